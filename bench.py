@@ -23,6 +23,9 @@ This file holds the driver's command line, the N = 1 headline path and the dispa
   benchlib/cpu_baseline.py, context.py, common.py   the host-side baselines (the oracle module is handed in from HERE: the only import of oracle/ outside tests/ and smoke()),
                          the stock torch-ROCm context legs, the shared plumbing
 
+--dump-outputs DIR (the N = 1 headline path): what the last timed step computed, as DIR/<name>.npy in float32 (benchlib.common.dump_outputs; the other paths refuse the flag); the inputs are seeded, so two
+runs with the same arguments — or two builds — can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (GEMM kernel vs the 5.033 POPS dense int8 MFMA peak, timed live with HIP events),
 `cpu_baseline` (the QSPEC pipeline around torch._int_mm on the host cores, rank 0, at every world size) and `verified`.
 """
@@ -32,13 +35,12 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # RCCL needs dmabuf IPC on this pool (already exported on the GPU boxes)
-
 import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from benchlib.common import PEAK_HBM_GBS, PEAK_INT8_TOPS, _claim_stdout, emit_json, graph_of, med, test_hooks, traffic_for  # noqa: E402
+from benchlib.common import PEAK_HBM_GBS, PEAK_INT8_TOPS, _claim_stdout, apply_graph_queue_default, dumped_outputs_entry, emit_json, graph_of, med, test_hooks, traffic_for  # noqa: E402
 from benchlib.launch import relay_launch, self_launch, supervise, supervisor_verdict  # noqa: E402,F401  (re-exported: tests/test_bench_supervisor.py)
 
 
@@ -85,11 +87,25 @@ def parse():
     ap.add_argument("--native-timeout", type=float, default=120.0,
                     help="tp over RCCL: seconds EACH leg that drives the native exchange (libpq_rccl.so) may take; when one does not finish, the fastest verified leg "
                          "among those that did (the torch.distributed legs run first) is printed with \"native_exchange\": \"hung\" (a multi-GPU run is never lost to a hung collective)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="qlinear on one GPU: after the timed blocks, write what the LAST timed step left in the step's output buffers — y, and K1's codes and scales behind it — "
+                         "as DIR/<name>.npy in float32 (below 64 MB in all: a fixed, seeded sample of the rows where an array is larger).  The inputs are seeded: with the "
+                         "same arguments two runs, or two builds, write comparable files")
+    args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "qlinear" or args.gpus != 1 or args.mode == "tp"):
+        ap.error("--dump-outputs is implemented for the headline path only (--workload qlinear on one GPU, not --mode tp)")
+    if args.dump_outputs:
+        try:        # now, not after the measurements
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            assert os.access(args.dump_outputs, os.W_OK | os.X_OK), "not writable"
+        except (OSError, AssertionError) as e:
+            ap.error(f"--dump-outputs {args.dump_outputs}: {e}")
+    return args
 
 
 def main():
     args = parse()
+    graph_streams = apply_graph_queue_default()      # (before any HIP call, here and in every child: a host that caps the hardware queues — benchlib.common.graph_queue_default)
     hooks = test_hooks()           # (tests only, from the environment: benchlib.common.test_hooks)
     script = os.path.abspath(__file__)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -217,6 +233,8 @@ def main():
         blocks.append(dt)
     blocks.sort()
     dt = blocks[len(blocks) // 2]
+    # --dump-outputs: the buffers as the last timed step left them, copied on the device now (everything below reuses them) and written after the measurements
+    dump = {"y": y.clone(), "x_codes": xq.clone(), "x_scale": xs.clone()} if args.dump_outputs else None
 
     # ---- verification of what was just timed (rank-local, outside the timed region): the step's y must be the bits torch's own ops give for QSPEC E1-E4 around
     # torch._int_mm on THIS GPU, from the step's own codes and scales (the int32 accumulator through hipBLASLt — exact integers, one answer; the epilogue is three
@@ -335,7 +353,7 @@ def main():
         "config": {"workload": f"qlinear M={M} N={N} K={K} bf16-in/int8-compute/bf16-out (BASELINE configs[1])",
                    "parallelism": f"dp{world} over tokens, replicated int8 weights, no collective",
                    "launch": f"hipgraph x{S} steps/replay" if g_main is not None else "eager",
-                   "collective_in_graph": None,
+                   "collective_in_graph": None, "graph_streams": graph_streams,
                    "repeats": R, "timed": f"median of {R} blocks of exactly {K_steps} steps (barrier + synchronize around each block, max over ranks)",
                    "warmup_seconds": args.warmup_seconds, "gemm_variant": variant},
         "verified": verified,
@@ -368,6 +386,9 @@ def main():
             out["gpu_context"]["speedup_vs_torch_rocm_int8_pipeline"] = round(t_pipe / t_stepc, 2)
             out["gpu_context"]["speedup_vs_torch_bf16_linear"] = round(out["gpu_context"]["torch_bf16_linear_us"] / t_stepc, 2)
     if rank == 0:
+        if dump is not None:
+            out["dumped_outputs"] = dumped_outputs_entry(args.dump_outputs, dump, "the step's buffers after the last timed step: y [M, N], K1's int8 codes [M, K] and row scales [M]; "
+                                                         "<name>_rows.npy = the kept rows of a sampled array (one sample for all arrays of M rows)")
         out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(M, N, K)     # rank 0, after every timed region, at every world size
         emit_json(out)
     if dist is not None:

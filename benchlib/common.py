@@ -67,6 +67,102 @@ def traffic_for(shape=None, key=None):
     return (v, tr.get("source_by_shape")) if v else (None, None)
 
 
+GRAPH_QUEUES = "DEBUG_HIP_FORCE_GRAPH_QUEUES"
+
+
+def graph_queue_default(environ):
+    """The value bench.py gives DEBUG_HIP_FORCE_GRAPH_QUEUES before HIP initialises, or None to leave the runtime alone; a pure function of the environment mapping.
+    HIP 7.0 replays a graph with parallel branches (the native_overlap legs of --mode tp fork to the communicator's side stream) on a pool of its own streams, 4 of them by
+    default, and while it hands them out it skips every pool stream that shares the launch stream's hardware queue WITHOUT looking for the end of the pool.  On a host that
+    caps the hardware queues of a process (GPU_MAX_HW_QUEUES) below 4, several pool streams share that queue, the walk leaves the pool and the first replay dies with SIGSEGV
+    inside hipGraphLaunch (met at a cap of 2, in the 4-block leg).  One graph stream needs no pool: "1" under such a cap.  The branches of a forked graph then run in capture
+    order on the launch stream — same nodes, same bits, NO overlap (the line says so: config.graph_streams, and the note of each overlap leg).  A value already set wins."""
+    cap = str(environ.get("GPU_MAX_HW_QUEUES") or "")
+    if environ.get(GRAPH_QUEUES) or not cap.isdigit() or not 0 < int(cap) < 4:
+        return None
+    return "1"
+
+
+def apply_graph_queue_default(environ=os.environ):
+    """Called at the top of bench.py's main(): after `import torch` (which only loads the HIP library; the runtime reads its switches when it initialises, at the first HIP
+    call) and before anything touches the GPU.  Not at import time: a process that merely imports bench keeps its environment.  Returns graph_streams() for the line."""
+    v = graph_queue_default(environ)
+    if v is not None:
+        environ[GRAPH_QUEUES] = v
+    return graph_streams(environ)
+
+
+def graph_streams(environ=os.environ):
+    """config.graph_streams of the JSON line: the streams a replayed graph may use (1 = the branches of a forked graph run one after the other), None = the runtime's default"""
+    v = str(environ.get(GRAPH_QUEUES) or "")
+    return int(v) if v.isdigit() else None
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6     # --dump-outputs: everything written stays below 64 MB
+DUMP_SAMPLE_SEED = 20240607
+
+
+def sample_rows(n_rows, bytes_per_row, budget_bytes, seed=DUMP_SAMPLE_SEED):
+    """The rows of an [n_rows, ...] output that --dump-outputs keeps: all of them when they fit the budget, otherwise a fixed sample — as many rows as fit, drawn
+    once from a seeded CPU generator (the same rows on every box and in every run) and sorted."""
+    keep = min(n_rows, max(1, budget_bytes // max(1, bytes_per_row)))
+    if keep >= n_rows:
+        return torch.arange(n_rows)
+    g = torch.Generator().manual_seed(seed)
+    return torch.randperm(n_rows, generator=g)[:keep].sort().values
+
+
+def dump_outputs(dirpath, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: write what the timed path computed as DIR/<name>.npy, float32 (every value the path produces — bf16 / fp16 / f32 outputs, int8 codes — is
+    exact in float32).  `arrays` maps a name to a 1-D or 2-D tensor.  2-D arrays with the same number of rows share ONE row sample (row i of y.npy and of x_codes.npy is the
+    same token): the budget left by the 1-D arrays is split evenly over the row counts (what a small group leaves goes to the larger ones), and a group that does not fit is cut down to sample_rows() of
+    its rows, the kept row indices beside each array as DIR/<name>_rows.npy.  Returns {file name: shape} for the JSON line."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    groups = {}
+    for name, t in arrays.items():
+        if t.dim() == 2:
+            groups.setdefault(t.shape[0], []).append(name)
+    left = budget_bytes - sum(4 * t.numel() for t in arrays.values() if t.dim() != 2)
+    per_row = {n_rows: sum(4 * arrays[n].shape[1] + 4 for n in names) for n_rows, names in groups.items()}       # (+ 4: the row's index in <name>_rows.npy)
+    rows_of, rest = {}, left
+    for i, n_rows in enumerate(sorted(groups, key=lambda r: r * per_row[r])):      # the smallest first: what a group that fits whole leaves goes to the larger ones
+        rows_of[n_rows] = sample_rows(n_rows, per_row[n_rows], rest // (len(groups) - i))
+        rest -= rows_of[n_rows].numel() * per_row[n_rows]
+    written, total = {}, 0
+
+    def save(name, t):
+        nonlocal total
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+        total += a.nbytes
+    for name, t in arrays.items():
+        if t.dim() == 2:
+            rows, stale = rows_of[t.shape[0]], os.path.join(dirpath, name + "_rows.npy")
+            if rows.numel() < t.shape[0]:
+                if total + 4 * rows.numel() * (t.shape[1] + 1) > left:
+                    raise ValueError(f"--dump-outputs: one row of {name} ({t.shape[1]} values) does not fit what is left of the {budget_bytes}-byte budget")
+                save(name + "_rows", rows)
+                t = t[rows.to(t.device)]
+            elif os.path.exists(stale):
+                os.remove(stale)               # (a directory used before, for a larger problem)
+        save(name, t)
+    return written
+
+
+def dumped_outputs_entry(dirpath, arrays, what):
+    """The line's `dumped_outputs`.  The files are written after every measurement, and a dump that fails then — the directory gone, the disk full — must not lose the line:
+    the entry carries the error instead of the files."""
+    entry = {"dir": os.path.abspath(dirpath), "dtype": "float32", "what": what}
+    try:
+        entry["files"] = dump_outputs(dirpath, arrays)
+    except Exception as e:
+        entry["error"] = f"{type(e).__name__}: {e}"[:300]
+        print(f"[bench] --dump-outputs failed: {entry['error']}", file=sys.stderr)
+    return entry
+
+
 _JSON_FD = None
 
 

@@ -6,7 +6,7 @@ import time
 
 import torch
 
-from .common import PEAK_HBM_GBS, PEAK_INT8_TOPS, emit_json, emit_marker, graph_of, test_hooks, traffic_for
+from .common import PEAK_HBM_GBS, PEAK_INT8_TOPS, emit_json, emit_marker, graph_of, graph_streams, test_hooks, traffic_for
 
 
 class _Watchdog:
@@ -68,6 +68,8 @@ def run_tp(args, world, rank, dev, dist, cpu_fn=None):
     from protoquant_amd.sharded import shard_bounds, gather_columns
     lib = L.lib()
     hooks = test_hooks()
+    # one graph stream (bench.py sets it on a host that caps the hardware queues: benchlib.common.graph_queue_default): a replayed graph runs its branches one after the other
+    serial_graph = graph_streams() == 1 and not args.no_graph
     M, N, K = args.M, args.N, args.K
     st = lambda: torch.cuda.current_stream().cuda_stream     # noqa: E731
     med = lambda v: sorted(v)[len(v) // 2]                   # noqa: E731
@@ -203,14 +205,15 @@ def run_tp(args, world, rank, dev, dist, cpu_fn=None):
         ag = shard_bytes / (XGMI_LINK_GBS * 1e3) if world > 1 else 2 * M * N / (LAYOUT_TBS * 1e6)     # world 1: a device-local copy
         lay = 0.0 if "transposed" in leg.name else 2 * (2 * M * N) / (LAYOUT_TBS * 1e6)
         C = leg.chunks
-        if C > 1:           # pipeline of C row blocks: the first block's GEMM and the last block's exchange are exposed, the rest runs at the slower of the two
+        if C > 1 and not serial_graph:    # pipeline of C row blocks: the first block's GEMM and the last block's exchange are exposed, the rest runs at the slower of the two
             c, e = (t_comp - t_k1_hot) / C, (ag + lay) / C
             step = t_k1_hot + c + (C - 1) * max(c, e) + e
         else:
             step = t_comp + ag + lay
         return {"compute_us": round(t_comp, 2), "allgather_us": round(ag, 2), "layout_pass_us": round(lay, 2), "step_us": round(step, 2),
                 "assumptions": f"per-rank shard {shard_bytes} B over one direct xGMI link per peer at {XGMI_LINK_GBS:.0f} GB/s, all {max(world - 1, 1)} links concurrently; "
-                               f"layout pass at {LAYOUT_TBS:.0f} TB/s; " + (f"{C} row blocks, exchange of block i under the GEMM of block i+1" if C > 1 else "no overlap of exchange and compute")
+                               f"layout pass at {LAYOUT_TBS:.0f} TB/s; " + (f"{C} row blocks, exchange of block i under the GEMM of block i+1" if C > 1 and not serial_graph else
+                                                 f"{C} row blocks replayed on ONE graph stream: no overlap of exchange and compute" if C > 1 else "no overlap of exchange and compute")
                                + " (DESIGN.md §6)"}
 
     def run_leg(leg):
@@ -338,7 +341,7 @@ def run_tp(args, world, rank, dev, dist, cpu_fn=None):
             "config": {"workload": f"qlinear M={M} N={N} K={K} bf16-in/int8-compute/bf16-out (BASELINE configs[1])",
                        "parallelism": f"tp{world}: W column-sharded ({n_local} of {N} output channels per rank), replicated activation, RCCL all-gather of the bf16 shards after dequant",
                        "headline_leg": head, "exchange": h["exchange"], "launch": h["launch"], "collective_in_graph": h["collective_in_graph"],
-                       "rccl_ranks": shared.get("rccl_ranks", dist.get_world_size()), "native": bool(h["native"]),
+                       "rccl_ranks": shared.get("rccl_ranks", dist.get_world_size()), "native": bool(h["native"]), "graph_streams": graph_streams(),
                        "repeats": R, "timed": f"per leg: median of {R} blocks of exactly {K_steps} steps (barrier + synchronize around each block, max over ranks); headline = the fastest "
                                               "leg that finished AND reproduced the unsharded qlinear bit for bit on every rank",
                        "warmup_seconds": args.warmup_seconds, "gemm_variant": variant},
@@ -447,7 +450,9 @@ def run_tp(args, world, rank, dev, dist, cpu_fn=None):
                     rg.gather_rows_async(y_loc, y_full, m0, m1, N)
                 rg.join(dev)
             lg = Leg(f"native_overlap{C}", f"libpq_rccl.so pq_allgather_cols_rows_async x{C} row blocks on the communicator's side stream + pq_comm_join", comp_c, comm_c,
-                     lambda: y_full, clear_rows, True, True, f"{C} row blocks: the exchange of block i runs under the GEMM of block i+1; the whole step in one hipGraph", chunks=C)
+                     lambda: y_full, clear_rows, True, True, (f"{C} row blocks, the whole step in one hipGraph replayed on ONE stream (graph_streams = 1: this host caps the hardware queues): each block's exchange runs "
+                      "between the GEMMs in capture order, nothing overlaps" if serial_graph else
+                      f"{C} row blocks: the exchange of block i runs under the GEMM of block i+1; the whole step in one hipGraph"), chunks=C)
             lg.step = step_c
             nat.append(lg)
         for leg in nat:
