@@ -52,7 +52,7 @@ const char* pq_last_error(void);
  * the layout pass), PQ_NO_TAILSPLIT, PQ_NO_SPLITK, PQ_FORCE_SPLITK (slice count: experiments), PQ_FSK (0 = no fused
  * split-K, S = S slices), PQ_FSK_SYMMETRIC and PQ_FSK_FENCED (see pq_qlinear_s8), PQ_NO_MIDM (no 64-row ring tiles), PQ_RING_ROT (0 = no K rotation), PQ_FAKE_CUS (plan as if the device had n CUs),
  * PQ_SKINNY_RB ("" = off / auto), PQ_EPI_ANY_ALIGN (0 = the staged epilogue only for 16-byte aligned output rows; default: any element-aligned row),
- * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes).  The environment variables of the same names are read ONCE, at the first call into the
+ * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes), PQ_GROUPED_TILE / PQ_GROUPED_ROT (see pq_qlinear_s8_grouped).  The environment variables of the same names are read ONCE, at the first call into the
  * library; this call changes a switch afterwards.
  * Threading: the switches live in an immutable snapshot; pq_set_option publishes a modified copy with one atomic pointer
  * swap, and every other entry point pins the snapshot that is live when it is ENTERED and plans and launches under that
@@ -189,6 +189,34 @@ const char* pq_kslabs_way_name(const int8_t* a, int64_t lda, int64_t slab_stride
 int32_t pq_qlinear_s8_kslabs(const int8_t* a, int64_t lda, int64_t slab_stride, int64_t k_per_slab, const float* a_scale, const int8_t* b, int64_t ldb,
                              const float* b_scale, const void* bias, void* y, int64_t ldy, int32_t out_dtype, int64_t M, int64_t N, int64_t K,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* GROUPED qlinear for mixture-of-experts layers — ONE launch over all E experts (gemm_s8_grouped.hip):
+ *   y[r, :] = cast_rne_out((f32(xq[src(r), :] . wq[e(r)]^T) * xs[r]) * ws[e(r)][:] (+ f32(bias[e(r)][:])))      for the rows r of a token list SORTED BY EXPERT:
+ * rows offsets[e] .. offsets[e + 1] - 1 belong to expert e.  Every output row has the bits pq_qlinear_s8 gives when it is run once per expert on that expert's row slice
+ * (same MFMA, exact integer sums, the same per-element epilogue).
+ *  - offsets: int32[E + 1] in DEVICE memory, non-decreasing, offsets[0] = 0, offsets[E] <= M_total.  The host never reads it (no copy, no synchronisation, no allocation):
+ *    the grid is sized from E and M_total alone, so a captured hipGraph stays valid when the CONTENTS of offsets (and of a_row_index) change between replays.  Rows
+ *    offsets[E] .. M_total - 1 of y are not written.  Values outside [0, M_total] are clamped by the kernel: wrong offsets give wrong results, never a wild access.
+ *  - a_row_index (nullable): int32[M_total] in device memory; grouped row r reads its codes from row a_row_index[r] of xq — the un-permuted [x_rows, K] code matrix, where a
+ *    token routed to top_k experts appears top_k times in the list — so no permuted copy of the codes is made.  Then x_rows * ldx < 2^32 (the loader's per-lane source
+ *    offset is 32 bits); indices are clamped into [0, x_rows).  Without it row r reads row r of xq (x_rows >= M_total).
+ *  - xs: row scales in GROUPED order, [M_total] (gathering 4 bytes per row is the caller's job).  wq: [E][N][K] int8, expert e at wq + e * w_expert_stride with leading
+ *    dimension ldw; ws: [E][N] column scales; bias: [E][N] in the output dtype, nullable.
+ *  - K a multiple of 128, ldx and ldw multiples of 16 (the modules pad K with zeros, as for pq_qlinear_s8's fast tiles), xq and wq 16-byte aligned, 1 <= E <= 1024.
+ *    M_total == 0 (or N == 0) is a no-op.  No workspace.
+ * Tiles: 64(m) x 128(n) or 64 x 64 loader / consumer ring tiles, chosen from the upper bound ceil(M_total / 64) + E of the m-tiles, N and the device's CU count
+ * (pq_grouped_variant_name; PQ_GROUPED_TILE = 64x128 | 64x64 forces one, PQ_GROUPED_ROT=1 rotates the K walk between the m-tiles of one expert — time only, never bits). */
+int32_t pq_qlinear_s8_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs,
+                              const int8_t* wq, int64_t ldw, int64_t w_expert_stride, const float* ws, const void* bias,
+                              const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                              void* y, int64_t ldy, int32_t out_dtype, void* stream);
+/* ... and its debug / parity twin: acc[r, :] = xq[src(r), :] . wq[e(r)]^T, exact int32 (pq_gemm_s8s8s32 per expert). */
+int32_t pq_gemm_s8s8s32_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows,
+                                const int8_t* wq, int64_t ldw, int64_t w_expert_stride,
+                                const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                                int32_t* acc, int64_t ldacc, void* stream);
+/* "grouped64x128_16x16x64" | "grouped64x64_16x16x64": the tile the grouped launch would use (static string). */
+const char* pq_grouped_variant_name(int32_t E, int64_t M_total, int64_t N, int64_t K);
 
 /* qlinear.forward in ONE call: y[M,N] = qlinear(x[M,K]) with dynamic per-token quantisation of x (K1), the int8 MFMA GEMM
  * and the fused dequant epilogue, output dtype = input dtype.  Scratch (xq, xs, optional split-K slabs) is carved from

@@ -22,6 +22,7 @@ EXPORTS = (
     "pq_rmsnorm_quant_rowwise", "pq_set_option", "pq_qlinear_s8_t", "pq_qlinear_t_workspace_bytes",
     "pq_silu_mul_rowamax", "pq_silu_mul_quant_rowwise_amax", "pq_qlinear_s8_kslabs", "pq_qlinear_kslabs_workspace_bytes", "pq_qlinear_kslabs_workspace_bytes_for", "pq_kslabs_way_name",
     "pq_quant_rowamax", "pq_quant_rowwise_amax",
+    "pq_qlinear_s8_grouped", "pq_gemm_s8s8s32_grouped", "pq_grouped_variant_name",
 )
 
 _lib = None
@@ -82,6 +83,12 @@ def lib() -> ctypes.CDLL:
     L.pq_kslabs_way_name.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i64, sz]
     L.pq_qlinear_s8_kslabs.restype = i32
     L.pq_qlinear_s8_kslabs.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]
+    L.pq_qlinear_s8_grouped.restype = i32
+    L.pq_qlinear_s8_grouped.argtypes = [vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, i32, i64, i64, i64, vp, i64, i32, vp]
+    L.pq_gemm_s8s8s32_grouped.restype = i32
+    L.pq_gemm_s8s8s32_grouped.argtypes = [vp, i64, vp, i64, vp, i64, i64, vp, i32, i64, i64, i64, vp, i64, vp]
+    L.pq_grouped_variant_name.restype = ctypes.c_char_p
+    L.pq_grouped_variant_name.argtypes = [i32, i64, i64, i64]
     L.pq_silu_mul_quant_rowwise.restype = i32
     L.pq_silu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_rmsnorm_quant_rowwise.restype = i32

@@ -22,6 +22,7 @@ template <int DT, int MODE, bool IDENT> void silu_mul_split_dispatch(const void*
 template <int OUT> void launch_gemm_ring128(const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t, int64_t a_slab_stride = 0, int64_t a_k_per_slab = 0);
 template <int OUT> void launch_gemm_ringt(int, const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t, int64_t a_slab_stride = 0, int64_t a_k_per_slab = 0);
 template <int OUT> void launch_gemm_skinny(const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t);
+template <int OUT> void launch_gemm_grouped(int, const int8_t*, int64_t, const int32_t*, int64_t, const int8_t*, int64_t, int64_t, const EpiArgs&, const int32_t*, int, int64_t, int64_t, int64_t, int, hipStream_t);
 bool gemm_fast_eligible(const int8_t*, int64_t, const int8_t*, int64_t, int64_t, int64_t, int64_t);
 template <int TM> void launch_gemm_splitk_i32(const int8_t*, int64_t, const int8_t*, int64_t, int32_t*, int64_t, int64_t, int64_t, int, hipStream_t, int nxcd);
 template <int OUT> void launch_splitk_reduce(const int32_t*, int, int64_t, int64_t, const EpiArgs&, hipStream_t);
@@ -80,7 +81,7 @@ thread_local int tl_depth = 0;
 
 // every behaviour switch, by name: the ONE place both the environment pass (once) and pq_set_option go through
 const char* const kOptionNames[] = {"PQ_FORCE_VARIANT", "PQ_NO_TAILSPLIT", "PQ_NO_SPLITK", "PQ_FORCE_SPLITK", "PQ_FSK", "PQ_FSK_SYMMETRIC", "PQ_FSK_FENCED", "PQ_FSK_COOP", "PQ_FAKE_CUS", "PQ_NO_MIDM", "PQ_NO_KSLABS", "PQ_NO_RING160", "PQ_MIDM_CT", "PQ_RMS_WAVE_MAX", "PQ_SILU_TPR", "PQ_SP128_LC",
-                                    "PQ_SP256_P3", "PQ_SP256_ASM", "PQ_SP256_PERSIST", "PQ_RING_LC", "PQ_RING_ROT", "PQ_K1_LDS", "PQ_EPI_ANY_ALIGN", "PQ_K2_BLOCKS_A", "PQ_K2_BLOCKS_E", "PQ_K1_RPW", "PQ_K1_ST16", "PQ_SKINNY_RB", "PQ_SKINNY_STAGE", "PQ_SKINNY_KS"};
+                                    "PQ_SP256_P3", "PQ_SP256_ASM", "PQ_SP256_PERSIST", "PQ_RING_LC", "PQ_RING_ROT", "PQ_K1_LDS", "PQ_EPI_ANY_ALIGN", "PQ_K2_BLOCKS_A", "PQ_K2_BLOCKS_E", "PQ_K1_RPW", "PQ_K1_ST16", "PQ_SKINNY_RB", "PQ_SKINNY_STAGE", "PQ_SKINNY_KS", "PQ_GROUPED_TILE", "PQ_GROUPED_ROT"};
 bool apply_option(pq::Options& o, const char* name, const char* value) {
     const bool set = value && *value;
     const int iv = set ? atoi(value) : 0;
@@ -114,6 +115,8 @@ bool apply_option(pq::Options& o, const char* name, const char* value) {
     else if (!strcmp(name, "PQ_SKINNY_STAGE")) o.skinny_stage = !(set && *value == '0');
     else if (!strcmp(name, "PQ_SKINNY_KS")) o.skinny_ks = iv > 0 ? iv : 0;
     else if (!strcmp(name, "PQ_SKINNY_RB")) o.skinny_rb = set && *value == '2' ? 2 : (set && *value == '1' ? 1 : 0);
+    else if (!strcmp(name, "PQ_GROUPED_TILE")) o.grouped_tile = !set ? 0 : (!strcmp(value, "64x128") ? 1 : (!strcmp(value, "64x64") ? 2 : 0));
+    else if (!strcmp(name, "PQ_GROUPED_ROT")) o.grouped_rot = set && *value == '1';
     else return false;
     return true;
 }
@@ -789,6 +792,83 @@ int32_t pq_qlinear_s8_kslabs(const int8_t* a, int64_t lda, int64_t slab_stride, 
     }
     const size_t rest = workspace_bytes - need_a;
     return pq_qlinear_s8(reinterpret_cast<const int8_t*>(flat), K, a_scale, b, ldb, b_scale, bias, y, ldy, out_dtype, M, N, K, rest ? flat + need_a : nullptr, rest, stream);
+}
+
+// ---- grouped GEMM over the experts of a mixture-of-experts layer (gemm_s8_grouped.hip)
+// tile of the grouped launch: 0 = 64(m) x 128(n), 1 = 64 x 64.  The host knows only the upper bound of the m-tiles, ceil(M_total / 64) + E.  pick_variant's rule for these
+// two tiles — rounds of the device's CUs x (0.95, 0.66), the measured time of one tile — reduces to: 64 x 64 exactly while its grid still fits ONE round of the CUs
+// ((2 r - 1) x 0.66 < r x 0.95 only for r = 1).  Those constants were measured on plain M x N grids on one fleet; for grouped grids, where up to E of the counted tiles
+// do not exist, the rule is unmeasured.
+static int grouped_plan(int32_t E, int64_t M_total, int64_t N) {
+    if (options().grouped_tile > 0) return options().grouped_tile - 1;
+    const int64_t mt = (M_total + 63) / 64 + E;
+    return mt * ((N + 63) / 64) <= device_cus() ? 1 : 0;
+}
+// everything pq_qlinear_s8_grouped and pq_gemm_s8s8s32_grouped have in common; no HIP call is made before the checks are through
+static int32_t grouped_check(const char* what, const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const int8_t* wq, int64_t ldw,
+                             int64_t w_expert_stride, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K, const void* y, int64_t ldy) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (E <= 0 || E > 1024) return fail(PQ_ERR_BAD_ARG, "%s: E = %d (1 .. 1024 experts)", what, E);
+    if (M_total < 0 || M_total >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: M_total = %lld", what, (long long)M_total);
+    if (N < 0 || N >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: N = %lld", what, (long long)N);
+    if (K < 128 || K % 128 != 0 || K >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: K = %lld must be a positive multiple of 128 (pad the codes with zeros)", what, (long long)K);
+    if (x_rows < 0 || x_rows >= ((int64_t)1 << 31)) return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld", what, (long long)x_rows);
+    if (ldx < K || ldx % 16 != 0 || ldx >= (1 << 23)) return fail(PQ_ERR_BAD_ARG, "%s: ldx = %lld (>= K, a multiple of 16, < 2^23)", what, (long long)ldx);
+    if (ldw < K || ldw % 16 != 0 || ldw >= (1 << 23)) return fail(PQ_ERR_BAD_ARG, "%s: ldw = %lld (>= K, a multiple of 16, < 2^23)", what, (long long)ldw);
+    if (w_expert_stride % 16 != 0 || (N > 0 && w_expert_stride < (N - 1) * ldw + K))
+        return fail(PQ_ERR_BAD_ARG, "%s: w_expert_stride = %lld (a multiple of 16, >= (N - 1) * ldw + K)", what, (long long)w_expert_stride);
+    if (ldy < N) return fail(PQ_ERR_BAD_ARG, "%s: ldy = %lld < N = %lld", what, (long long)ldy, (long long)N);
+    if (!offsets) return fail(PQ_ERR_BAD_ARG, "%s: offsets is null", what);
+    if (M_total > 0 && N > 0 && (!xq || !wq || !y)) return fail(PQ_ERR_BAD_ARG, "%s: %s is null", what, !xq ? "xq" : (!wq ? "wq" : "y"));
+    if (!al16(xq) || !al16(wq)) return fail(PQ_ERR_BAD_ARG, "%s: %s must be 16-byte aligned", what, !al16(xq) ? "xq" : "wq");
+    if (a_row_index) {
+        // the loader's per-lane source offset is 32 bits (a_row_index[r] * ldx + 16 * chunk): the address math in the K loop is not widened for larger operands
+        if (x_rows < 1) return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld with a_row_index", what, (long long)x_rows);
+        if (x_rows * ldx >= ((int64_t)1 << 32)) return fail(PQ_ERR_BAD_ARG, "%s: x_rows * ldx = %lld >= 2^32 with a_row_index", what, (long long)(x_rows * ldx));
+    } else if (x_rows < M_total) {
+        return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld < M_total = %lld without a_row_index", what, (long long)x_rows, (long long)M_total);
+    }
+    return PQ_OK;
+}
+
+int32_t pq_qlinear_s8_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs, const int8_t* wq, int64_t ldw,
+                              int64_t w_expert_stride, const float* ws, const void* bias, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                              void* y, int64_t ldy, int32_t out_dtype, void* stream) {
+    Range range_("pq:qlinear_s8_grouped (K3+K4)");
+    if (out_dtype < 0 || out_dtype > 2) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_s8_grouped: unknown out_dtype %d", out_dtype);
+    if (const int32_t st = grouped_check("pq_qlinear_s8_grouped", xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, offsets, E, M_total, N, K, y, ldy)) return st;
+    if (M_total > 0 && N > 0 && (!xs || !ws)) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_s8_grouped: %s is null", !xs ? "xs" : "ws");
+    if (M_total == 0 || N == 0) return PQ_OK;
+    pq::EpiArgs epi{xs, ws, bias, y, ldy, 0};
+    epi.y_any_align = options().epi_any_align ? 1 : 0;
+    epi.nxcd = device_xcds();
+    const int tile = grouped_plan(E, M_total, N), rot = options().grouped_rot ? 1 : 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (out_dtype) {
+        case PQ_BF16: pq::launch_gemm_grouped<PQ_BF16>(tile, xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, rot, st); break;
+        case PQ_FP16: pq::launch_gemm_grouped<PQ_FP16>(tile, xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, rot, st); break;
+        default: pq::launch_gemm_grouped<PQ_F32>(tile, xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, rot, st); break;
+    }
+    return check_launch("pq_qlinear_s8_grouped");
+}
+
+int32_t pq_gemm_s8s8s32_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const int8_t* wq, int64_t ldw, int64_t w_expert_stride,
+                                const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K, int32_t* acc, int64_t ldacc, void* stream) {
+    Range range_("pq:gemm_s8s8s32_grouped (K3)");
+    if (const int32_t st = grouped_check("pq_gemm_s8s8s32_grouped", xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, offsets, E, M_total, N, K, acc, ldacc)) return st;
+    if (M_total == 0 || N == 0) return PQ_OK;
+    pq::EpiArgs epi{nullptr, nullptr, nullptr, acc, ldacc, 0};
+    epi.y_any_align = options().epi_any_align ? 1 : 0;
+    epi.nxcd = device_xcds();
+    pq::launch_gemm_grouped<pq::OUT_I32>(grouped_plan(E, M_total, N), xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K,
+                                         options().grouped_rot ? 1 : 0, static_cast<hipStream_t>(stream));
+    return check_launch("pq_gemm_s8s8s32_grouped");
+}
+
+const char* pq_grouped_variant_name(int32_t E, int64_t M_total, int64_t N, int64_t K) {
+    CallScope scope_;
+    (void)K;      // (both tiles step through K in the same 128-byte K-tiles)
+    return grouped_plan(E, M_total, N) == 0 ? "grouped64x128_16x16x64" : "grouped64x64_16x16x64";
 }
 
 // ---- one-call dynamic qlinear: K1 (x -> xq, xs in the workspace) then pq_qlinear_s8 (with split-K slabs if planned).

@@ -52,6 +52,8 @@ struct Options {
     bool sp256_persist = false;
     int silu_tpr = 0;                // 0 auto; 256 forces the 256-thread layout on wide rows
     int rms_wave_max = 256;
+    int grouped_tile = 0;            // PQ_GROUPED_TILE: tile of the grouped GEMM (gemm_s8_grouped.hip): 0 = by plan, 1 = "64x128", 2 = "64x64" (tests, experiments)
+    bool grouped_rot = false;        // PQ_GROUPED_ROT=1: K rotation between the m-tiles of one expert that share a weight panel (time only, never bits; off until measured)
     int (*roctx_push)(const char*) = nullptr;      // PQ_ROCTX=1 (environment only)
     int (*roctx_pop)() = nullptr;
 };

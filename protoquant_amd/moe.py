@@ -1,0 +1,235 @@
+"""Mixture-of-experts layers on the int8 path: the E expert MLPs of a decoder block as TWO grouped GEMM launches (qlinear_s8_grouped: one launch over all experts)
+instead of 3 E launches of qlinear, and ONE activation quantisation instead of one per expert.
+
+GroupedQLinear   E experts' linear layers as one [E, N, K] int8 weight + [E, N] scales (+ bias)
+MoEGatedMLP      forward(hidden[T, H], topk_ids[T, k], topk_weights[T, k]): quantise once -> sort the (token, slot) pairs by expert on the device -> grouped gate+up GEMM
+                 reading the codes through a row index -> silu_mul_quantize -> grouped down GEMM -> combine
+swap_moe_experts replaces blocks shaped like Mixtral's / Qwen-MoE's sparse MoE block (a ModuleList `experts` of gated MLPs + a router `gate`)
+
+Routing (softmax, top-k, the sort, the offsets) and the combine are stock torch ops — plumbing, as attention and the residual adds are; the GEMMs and the quantisations are
+the library's kernels.  Nothing here reads a routing result on the host: the forward is capturable into a hipGraph and replayable for other routings."""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import _lib as L
+from .qlinear import FusedQLinear, GatedMLP, _is_silu, _KPadded, _round_k, qlinear, qlinear_s8_grouped
+from .qtensor import QTensor, quantize, silu_mul_quantize
+
+
+class GroupedQLinear(_KPadded, nn.Module):
+    """E linear layers of one shape held together: wq int8 [E, N, K], ws f32 [E, N], bias [E, N] or None.  in_features that is not a multiple of 128 is served as in
+    qlinear (_KPadded): a zero-padded copy of the weight, made lazily, and zero-tailed activation codes — same bits."""
+
+    def __init__(self, num_experts: int, in_features: int, out_features: int, bias: bool = False, device=None, dtype=None):
+        super().__init__()
+        self.num_experts, self.in_features, self.out_features = num_experts, in_features, out_features
+        dtype = dtype or torch.bfloat16
+        self.register_buffer("wq", torch.zeros((num_experts, out_features, in_features), dtype=torch.int8, device=device))
+        self.register_buffer("ws", torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
+        if bias:
+            self.register_buffer("bias", torch.zeros((num_experts, out_features), dtype=dtype, device=device))
+        else:
+            self.bias = None
+
+    @classmethod
+    def _from_parts(cls, wq: torch.Tensor, ws: torch.Tensor, bias) -> "GroupedQLinear":
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.num_experts, m.out_features, m.in_features = wq.shape
+        m.register_buffer("wq", wq.contiguous())
+        m.register_buffer("ws", ws.contiguous())
+        if bias is not None:
+            m.register_buffer("bias", bias.contiguous())
+        else:
+            m.bias = None
+        return m
+
+    @classmethod
+    def from_linears(cls, linears) -> "GroupedQLinear":
+        """One expert per element: an nn.Linear (quantised per output channel, as qlinear.from_linear) or an existing qlinear / FusedQLinear, whose codes and scales are
+        stacked as they are — nothing is quantised twice."""
+        parts = [l if hasattr(l, "wq") else qlinear.from_linear(l) for l in linears]
+        if not parts:
+            raise ValueError("GroupedQLinear.from_linears: no experts")
+        if any(p.wq.shape != parts[0].wq.shape for p in parts) or any((p.bias is None) != (parts[0].bias is None) for p in parts):
+            raise ValueError("GroupedQLinear.from_linears: the experts must share one shape, and all or none may have a bias")
+        return cls._from_parts(torch.stack([p.wq for p in parts]), torch.stack([p.ws for p in parts]),
+                               torch.stack([p.bias for p in parts]) if parts[0].bias is not None else None)
+
+    @classmethod
+    def from_weight(cls, weight: torch.Tensor, bias=None) -> "GroupedQLinear":
+        """A 3-D expert parameter weight[E, N, K] (y_e = x @ weight[e].T): per-output-channel quantisation of every expert in one pass — kernel K1 over the E * N rows of
+        the flattened weight, the bits per-expert quantisation gives.  bias: [E, N] or None."""
+        w = weight.detach()
+        L.require_gpu(w, "GroupedQLinear.from_weight(weight)")
+        if w.dim() != 3:
+            raise ValueError("from_weight expects a 3-D [E, N, K] weight")
+        E, N, K = w.shape
+        q = quantize(w.reshape(E * N, K), axis=-1)
+        return cls._from_parts(q.int_data.reshape(E, N, K), q.scale.reshape(E, N), bias.detach().clone() if bias is not None else None)
+
+    def codes_for_gemm(self, codes: torch.Tensor) -> torch.Tensor:
+        """int8 [R, in_features] -> the operand the grouped GEMM reads: itself, or a zero-tailed copy of the next multiple of 128 columns"""
+        K, kp = self.in_features, _round_k(self.in_features)
+        if kp == K:
+            return codes
+        buf = torch.empty((codes.shape[0], kp), dtype=torch.int8, device=codes.device)
+        buf[:, :K].copy_(codes)
+        buf[:, K:].zero_()
+        return buf
+
+    def forward(self, xq: QTensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, xs: torch.Tensor | None = None) -> torch.Tensor:
+        """xq: per-token QTensor [R, in_features].  Without row_index its rows are the grouped rows themselves; with it grouped row r reads row row_index[r] of xq and xs
+        carries the row scales already gathered into grouped order (default: gathered here).  Returns y[M_total, out_features] in xq.orig_dtype."""
+        if not isinstance(xq, QTensor) or xq.axis != 1 or xq.shape[-1] != self.in_features:
+            raise ValueError("GroupedQLinear: input must be a per-token QTensor [R, in_features]")
+        codes = self.codes_for_gemm(xq.int_data.reshape(-1, self.in_features))
+        if xs is None:
+            xs = xq.scale if row_index is None else xq.scale.index_select(0, row_index)
+        wq, _ = self._wq_for_gemm()
+        return qlinear_s8_grouped(codes, xs, wq, self.ws, self.bias, offsets, xq.orig_dtype, row_index=row_index)
+
+    def extra_repr(self):
+        return f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+
+
+def route_plan(topk_ids: torch.Tensor, num_experts: int):
+    """The (token, slot) pairs of a routing sorted by expert — pure tensor code, runs on any device, reads nothing on the host.
+    topk_ids: integer [T, k], every id in [0, num_experts).  Returns
+      row_index  int32 [T * k]  the token of grouped row r (stable sort: inside an expert the pairs keep their (token, slot) order)
+      offsets    int32 [E + 1]  rows offsets[e] .. offsets[e + 1] - 1 belong to expert e
+      rows_of    int64 [T, k]   the grouped rows of token t, ordered by EXPERT id (the order in which an eager loop over the experts adds them up)
+      slot_of    int64 [T, k]   the slot j of topk_ids[t] each of those rows came from (to pick the routing weight)"""
+    T, k = topk_ids.shape
+    flat = topk_ids.reshape(-1).to(torch.int64)
+    sorted_ids, order = torch.sort(flat, stable=True)
+    row_index = torch.div(order, k, rounding_mode="floor").to(torch.int32)
+    edges = torch.arange(num_experts + 1, device=flat.device, dtype=torch.int64)
+    offsets = torch.searchsorted(sorted_ids, edges, right=False).to(torch.int32)      # (bincount + cumsum without bincount's device -> host read of the largest id)
+    pos = torch.empty_like(order)
+    pos[order] = torch.arange(T * k, device=flat.device, dtype=torch.int64)           # grouped row of pair t * k + j (a permutation: no duplicate index)
+    slot_of = torch.argsort(topk_ids.to(torch.int64), dim=1, stable=True)
+    rows_of = pos.reshape(T, k).gather(1, slot_of)
+    return row_index, offsets, rows_of, slot_of
+
+
+def combine(y: torch.Tensor, rows_of: torch.Tensor, slot_of: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum over the experts of token t, in ascending expert id, of y[row] * w, every product and every partial sum rounded to y's dtype, starting from zero: the
+    bits of `final = zeros; for e in range(E): final.index_add_(0, tokens_e, out_e * w_e[:, None])`.  Deterministic: a gather and k adds, no atomics."""
+    T, k = rows_of.shape
+    w = topk_weights.to(y.dtype).gather(1, slot_of)
+    parts = y.index_select(0, rows_of.reshape(-1)).reshape(T, k, y.shape[1])
+    acc = torch.zeros((T, y.shape[1]), dtype=y.dtype, device=y.device)
+    for s in range(k):
+        acc = acc + parts[:, s] * w[:, s, None]
+    return acc
+
+
+class MoEGatedMLP(nn.Module):
+    """The E gated expert MLPs of a mixture-of-experts block: out[t] = sum_j w[t, j] * down_e(silu(gate_e(x_t)) * up_e(x_t)), e = topk_ids[t, j].
+    gate_up: GroupedQLinear [E, 2 I, H] (gate rows, then up rows, per expert); down: GroupedQLinear [E, H, I]."""
+
+    def __init__(self, gate_up: GroupedQLinear, down: GroupedQLinear):
+        super().__init__()
+        if gate_up.num_experts != down.num_experts or gate_up.out_features != 2 * down.in_features:
+            raise ValueError("MoEGatedMLP: gate_up must map to 2 x down.in_features, for the same experts")
+        self.gate_up, self.down = gate_up, down
+        self.num_experts = gate_up.num_experts
+
+    @classmethod
+    def from_experts(cls, experts) -> "MoEGatedMLP":
+        """experts: GatedMLP modules (their codes are stacked as they are) or (gate, up, down) triples of nn.Linear."""
+        mlps = [e if isinstance(e, GatedMLP) else GatedMLP.from_linears(*e) for e in experts]
+        return cls(GroupedQLinear.from_linears([m.gate_up for m in mlps]), GroupedQLinear.from_linears([m.down for m in mlps]))
+
+    def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
+        H = hidden.shape[-1]
+        x2 = hidden.reshape(-1, H)
+        T = x2.shape[0]
+        ids, w = topk_ids.reshape(T, -1), topk_weights.reshape(T, -1)
+        inter = self.down.in_features
+        xq = quantize(x2, axis=-1)                                     # ONE quantisation for all experts
+        row_index, offsets, rows_of, slot_of = route_plan(ids, self.num_experts)
+        gu = self.gate_up(xq, offsets, row_index)                      # [T k, 2 I]: the codes are read where the tokens lie
+        h = silu_mul_quantize(gu[:, :inter], gu[:, inter:])            # sorted rows: int8 codes + row scales
+        y = self.down(h, offsets)
+        return combine(y, rows_of, slot_of, w).reshape(hidden.shape)
+
+
+class MoEBlock(nn.Module):
+    """What swap_moe_experts puts in place of a sparse MoE block: the block's own router (`gate`) and routing recipe — softmax over the experts in f32, top-k,
+    optional renormalisation, weights cast to the hidden dtype — in front of MoEGatedMLP."""
+
+    def __init__(self, gate: nn.Module, experts: MoEGatedMLP, top_k: int, renormalise: bool, return_router_logits: bool):
+        super().__init__()
+        self.gate, self.experts = gate, experts
+        self.top_k, self.renormalise, self.return_router_logits = top_k, renormalise, return_router_logits
+
+    def forward(self, hidden_states: torch.Tensor):
+        x2 = hidden_states.reshape(-1, hidden_states.shape[-1])
+        router_logits = self.gate(x2)
+        weights = torch.softmax(router_logits, dim=1, dtype=torch.float)
+        weights, selected = torch.topk(weights, self.top_k, dim=-1)
+        if self.renormalise:
+            weights = weights / weights.sum(dim=-1, keepdim=True)
+        out = self.experts(x2, selected, weights.to(hidden_states.dtype)).reshape(hidden_states.shape)
+        return (out, router_logits) if self.return_router_logits else out
+
+
+_EXPERT_NAMES = (("gate_proj", "up_proj", "down_proj"), ("w1", "w3", "w2"))
+
+
+def _expert_linears(mod: nn.Module):
+    """(gate, up, down) of a gated expert MLP with a silu — Llama-style names or Mixtral's w1 / w3 / w2 — or None"""
+    for names in _EXPERT_NAMES:
+        g, u, d = (getattr(mod, n, None) for n in names)
+        if all(isinstance(l, nn.Linear) for l in (g, u, d)):
+            if not _is_silu(getattr(mod, "act_fn", None)) or len(list(mod.children())) > 4:
+                return None
+            if g.in_features != u.in_features or g.out_features != u.out_features or d.in_features != g.out_features or d.out_features != g.in_features:
+                return None
+            if (g.bias is None) != (u.bias is None):
+                return None
+            return g, u, d
+    return None
+
+
+def moe_block_parts(mod: nn.Module):
+    """A module shaped like a sparse MoE block — exactly two children, a ModuleList `experts` of gated silu MLPs of one shape and a Linear router `gate` with one
+    output per expert, and a top-k count among its attributes — as (experts' linears, top_k, renormalise, return_router_logits); else None.  Recognised by shape,
+    not by import (no dependency on transformers)."""
+    experts, gate = getattr(mod, "experts", None), getattr(mod, "gate", None)
+    if not isinstance(experts, nn.ModuleList) or len(experts) == 0 or not isinstance(gate, nn.Linear) or gate.out_features != len(experts):
+        return None
+    if {n for n, _ in mod.named_children()} != {"experts", "gate"}:
+        return None                                   # (shared experts, gates on the shared path, ...: not this block)
+    top_k = getattr(mod, "top_k", None)
+    if top_k is None:
+        top_k = getattr(mod, "num_experts_per_tok", None)
+    if not isinstance(top_k, int) or not 1 <= top_k <= len(experts):
+        return None
+    lins = [_expert_linears(e) for e in experts]
+    if any(l is None for l in lins) or any(l[0].weight.shape != lins[0][0].weight.shape or (l[2].bias is None) != (lins[0][2].bias is None) or
+                                           (l[0].bias is None) != (lins[0][0].bias is None) for l in lins):
+        return None
+    # Mixtral renormalises the top-k weights always; Qwen-MoE-style blocks say so in norm_topk_prob
+    renorm = bool(getattr(mod, "norm_topk_prob", True))
+    returns_logits = bool(getattr(mod, "return_router_logits", type(mod).__name__.endswith("SparseMoeBlock")))
+    return lins, top_k, renorm, returns_logits
+
+
+def swap_moe_experts(model: nn.Module) -> int:
+    """Replace, in place, every sparse MoE block of the model (moe_block_parts) by MoEBlock: the experts' weights are quantised per output channel and stacked, the
+    router stays what it was.  Returns the number of blocks replaced (0: a dense model is left untouched)."""
+    n = 0
+    for name, child in list(model.named_children()):
+        parts = moe_block_parts(child)
+        if parts is None:
+            n += swap_moe_experts(child)
+            continue
+        lins, top_k, renorm, returns_logits = parts
+        setattr(model, name, MoEBlock(child.gate, MoEGatedMLP.from_experts(lins), top_k, renorm, returns_logits))
+        n += 1
+    return n

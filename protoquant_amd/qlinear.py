@@ -198,6 +198,82 @@ def qlinear_s8_kslabs(xq_stacked: torch.Tensor, xs: torch.Tensor, wq: torch.Tens
     return y
 
 
+def _grouped_operands(what: str, xq, wq, offsets, row_index):
+    """Shared checks of the grouped entry points: xq int8 [R, K] row-major, wq int8 [E, N, K] (K contiguous, one stride between experts), offsets int32 [E + 1] and
+    row_index int32 [M_total] contiguous device vectors.  Returns (xq, wq, E, N, K, M_total)."""
+    L.require_gpu(xq, f"{what}(xq)")
+    xq = L.row_major_2d(xq)
+    dev = xq.device
+    _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
+    if wq.dim() != 3:
+        raise ValueError(f"{what}: wq must be int8 [E, N, K], got shape {tuple(wq.shape)}")
+    E, N, K = wq.shape
+    if xq.shape[1] != K:
+        raise ValueError(f"shape mismatch: x has K={xq.shape[1]}, the experts' weights have K={K}")
+    if K % 128 != 0 or K == 0:
+        raise ValueError(f"{what}: K = {K} must be a positive multiple of 128 (GroupedQLinear pads its weights; pad the codes with zeros)")
+    if (K > 1 and wq.stride(2) != 1) or (N > 1 and wq.stride(1) < K) or (E > 1 and wq.stride(0) < N * wq.stride(1)):
+        wq = wq.contiguous()
+    _check_operand(offsets, "offsets", dev, torch.int32, E + 1)
+    if row_index is not None:
+        if row_index.dim() != 1:
+            raise ValueError(f"row_index must be a vector, got shape {tuple(row_index.shape)}")
+        _check_operand(row_index, "row_index", dev, torch.int32, row_index.numel())
+        M_total = row_index.numel()
+    else:
+        M_total = xq.shape[0]
+    return xq, wq, E, N, K, M_total
+
+
+def qlinear_s8_grouped(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, offsets: torch.Tensor, out_dtype,
+                       row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The fused int8 GEMM + dequant epilogue over ALL experts of a mixture-of-experts layer in one launch (C-ABI pq_qlinear_s8_grouped): the rows are a token list sorted by
+    expert, rows offsets[e] .. offsets[e + 1] - 1 (int32 [E + 1], on the device — it is never read on the host) go through expert e's weight wq[e] ([E, N, K] int8),
+    scales ws[e] ([E, N]) and bias[e].  row_index (int32 [M_total], optional): row r reads its codes from row row_index[r] of xq, the un-permuted [T, K] code matrix;
+    without it xq is already in grouped order.  xs [M_total] is always in grouped order.  Every row has the bits of qlinear_s8 run per expert on its row slice; rows
+    >= offsets[E] of the output are left untouched."""
+    xq, wq, E, N, K, M = _grouped_operands("qlinear_s8_grouped", xq, wq, offsets, row_index)
+    dev = xq.device
+    code = L.dtype_code(out_dtype)
+    _check_operand(xs, "xs", dev, torch.float32, M)
+    _check_operand(ws, "ws", dev, torch.float32)
+    if tuple(ws.shape) != (E, N) or not ws.is_contiguous():
+        raise ValueError(f"ws must be a contiguous [{E}, {N}] tensor, got shape {tuple(ws.shape)} stride {ws.stride()}")
+    if bias is not None:
+        if bias.dtype != out_dtype:
+            bias = bias.to(out_dtype)
+        _check_operand(bias, "bias", dev, out_dtype)
+        if tuple(bias.shape) != (E, N) or not bias.is_contiguous():
+            raise ValueError(f"bias must be a contiguous [{E}, {N}] tensor, got shape {tuple(bias.shape)} stride {bias.stride()}")
+    if out is not None:
+        _check_operand(out, "out", dev, out_dtype)
+        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
+    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().pq_qlinear_s8_grouped(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0], xs.data_ptr(),
+                                              wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K), ws.data_ptr(),
+                                              bias.data_ptr() if bias is not None else None, offsets.data_ptr(), E, M, N, K, y.data_ptr(), L.ld(y), code,
+                                              L.stream_ptr(xq)), "qlinear_s8_grouped")
+    return y
+
+
+def int_mm_grouped(xq: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The exact int32 accumulators of qlinear_s8_grouped (C-ABI pq_gemm_s8s8s32_grouped): acc[r] = xq[src(r)] . wq[e(r)]^T — int_mm per expert, in one launch."""
+    xq, wq, E, N, K, M = _grouped_operands("int_mm_grouped", xq, wq, offsets, row_index)
+    dev = xq.device
+    if out is not None:
+        _check_operand(out, "out", dev, torch.int32)
+        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
+    acc = out if out is not None else torch.empty((M, N), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().pq_gemm_s8s8s32_grouped(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0],
+                                                wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K),
+                                                offsets.data_ptr(), E, M, N, K, acc.data_ptr(), L.ld(acc), L.stream_ptr(xq)), "int_mm_grouped")
+    return acc
+
+
 def qlinear_dyn(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias=None) -> torch.Tensor:
     """x[..., K] -> y[..., N]: dynamic per-token quant + int8 GEMM + fused dequant in ONE C-ABI call (pq_qlinear_dyn);
     the scratch (xq, xs, split-K slabs) lives in the per-device workspace."""
@@ -251,8 +327,8 @@ class _KPadded:
         key = (wq._version, wq.device, tuple(wq.shape), wq.data_ptr(), wq.storage_offset())
         c = self.__dict__.get("_wq_pad")
         if c is None or c[0] != key or c[2]() is not wq:
-            w = wq.new_zeros((wq.shape[0], kp))
-            w[:, :K].copy_(wq)
+            w = wq.new_zeros((*wq.shape[:-1], kp))          # ([N, K], or GroupedQLinear's [E, N, K])
+            w[..., :K].copy_(wq)
             c = (key, w, weakref.ref(wq))
             self.__dict__["_wq_pad"] = c
         return c[1], kp

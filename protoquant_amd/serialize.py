@@ -11,6 +11,8 @@ Format ``protoquant_amd.int8.v1`` — a flat ``state_dict``:
 fused projections          ``<parent>.<name>.wq`` = the members' codes concatenated along N (scales likewise): per-row
                            quantisation makes the concatenation exact
 gated MLP                  ``<mlp>.gate_up.{wq,ws}`` (gate then up) and ``<mlp>.down.{wq,ws}`` — the GatedMLP layout
+MoE experts                ``<block>.experts.gate_up.{wq,ws}`` int8 ``[E, 2I, H]`` / fp32 ``[E, 2I]`` and ``<block>.experts.down.{wq,ws}``
+                           ``[E, H, I]`` / ``[E, H]`` — the buffers of a block swapped by ``swap_moe_experts`` (its ``state_dict()``)
 column shard (rank r of G) rows ``shard_bounds(N, G, r)`` of ``wq`` / ``ws`` / ``bias`` under ``<mod>.local.*``
 row shard (rank r of G)    columns ``shard_bounds(K, G, r)`` of ``wq``, the FULL-row ``ws``, the bias on rank 0 only, under
                            ``<mod>.local.*``
@@ -29,6 +31,7 @@ import torch
 from torch import nn
 
 from .qlinear import FusedQLinear, GatedMLP, _is_silu, qlinear
+from .moe import GroupedQLinear, MoEBlock, MoEGatedMLP, moe_block_parts
 from .qtensor import quantize
 from .sharded import ColumnShardedQLinear, RowShardedQLinear, ShardedGatedMLP, shard_bounds
 
@@ -179,6 +182,18 @@ def empty_gated_mlp(hidden: int, intermediate: int, bias: bool = False, dtype=to
     return GatedMLP(empty_fused(hidden, (intermediate, intermediate), bias, dtype, device), empty_qlinear(intermediate, hidden, bias, dtype, device))
 
 
+def empty_grouped_qlinear(num_experts: int, in_features: int, out_features: int, bias: bool = False, dtype=torch.bfloat16, device=None) -> GroupedQLinear:
+    return GroupedQLinear(num_experts, in_features, out_features, bias=bias, device=device, dtype=dtype)
+
+
+def empty_moe_gated_mlp(num_experts: int, hidden: int, intermediate: int, bias: bool = False, down_bias: bool | None = None, dtype=torch.bfloat16,
+                        device=None) -> MoEGatedMLP:
+    """The receiving module of a swapped MoE block's experts: ``<block>.experts.gate_up.{wq,ws}`` [E, 2 I, H] / [E, 2 I] (gate rows then up rows, per expert) and
+    ``<block>.experts.down.{wq,ws}`` [E, H, I] / [E, H] — what ``swap_moe_experts(model).state_dict()`` holds."""
+    return MoEGatedMLP(empty_grouped_qlinear(num_experts, hidden, 2 * intermediate, bias, dtype, device),
+                       empty_grouped_qlinear(num_experts, intermediate, hidden, bias if down_bias is None else down_bias, dtype, device))
+
+
 def empty_column_sharded(in_features: int, out_features: int, bias: bool, world: int, rank: int, dtype=torch.bfloat16, device=None,
                          group=None, **kw) -> ColumnShardedQLinear:
     lo, hi = shard_bounds(out_features, world, rank)
@@ -200,11 +215,21 @@ def empty_sharded_gated_mlp(hidden: int, intermediate: int, world: int, rank: in
 
 
 def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False) -> nn.Module:
-    """The structural half of swap_linears(): replace every nn.Linear (and, with fuse_gated_mlp, every Llama-style MLP) by an
-    EMPTY int8 module of the same shape — no quantisation, no float weights needed (works on meta-device models) — so that
+    """The structural half of swap_linears() and swap_moe_experts(): replace every nn.Linear (and, with fuse_gated_mlp, every Llama-style MLP; and every sparse
+    MoE block swap_moe_experts would swap) by an EMPTY int8 module of the same shape — no quantisation, no float weights needed (works on meta-device models) — so that
     ``model.load_state_dict(convert_checkpoint(...))`` fills it.  Empty buffers live on the linear's device unless it is meta,
     then on the CPU; move the model to the GPU after loading."""
     for name, child in list(model.named_children()):
+        moe = moe_block_parts(child) if (predicate is None or predicate(name, child)) else None
+        if moe is not None:
+            # a block swap_moe_experts would swap: the same wrapper around EMPTY stacked experts (the router stays a float nn.Linear, as swap_moe_experts leaves it),
+            # so the state_dict of a swapped model loads without the float expert weights
+            lins, top_k, renorm, returns_logits = moe
+            g, _, d = lins[0]
+            dev = None if g.weight.device.type == "meta" else g.weight.device
+            experts = empty_moe_gated_mlp(len(lins), g.in_features, g.out_features, g.bias is not None, d.bias is not None, g.weight.dtype, dev)
+            setattr(model, name, MoEBlock(child.gate, experts, top_k, renorm, returns_logits))
+            continue
         if fuse_gated_mlp and (predicate is None or predicate(name, child)):
             g, u, d = (getattr(child, n, None) for n in ("gate_proj", "up_proj", "down_proj"))
             if all(isinstance(l, nn.Linear) for l in (g, u, d)) and _is_silu(getattr(child, "act_fn", None)) and \
