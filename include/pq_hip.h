@@ -52,7 +52,8 @@ const char* pq_last_error(void);
  * the layout pass), PQ_NO_TAILSPLIT, PQ_NO_SPLITK, PQ_FORCE_SPLITK (slice count: experiments), PQ_FSK (0 = no fused
  * split-K, S = S slices), PQ_FSK_SYMMETRIC and PQ_FSK_FENCED (see pq_qlinear_s8), PQ_NO_MIDM (no 64-row ring tiles), PQ_RING_ROT (0 = no K rotation), PQ_FAKE_CUS (plan as if the device had n CUs),
  * PQ_SKINNY_RB ("" = off / auto), PQ_EPI_ANY_ALIGN (0 = the staged epilogue only for 16-byte aligned output rows; default: any element-aligned row),
- * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes), PQ_GROUPED_TILE / PQ_GROUPED_ROT (see pq_qlinear_s8_grouped).  The environment variables of the same names are read ONCE, at the first call into the
+ * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes), PQ_GROUPED_TILE / PQ_GROUPED_ROT (see pq_qlinear_s8_grouped).  The switches that change launch geometry or pick another kernel for the same result are checked bit for bit in
+ * tests/test_gpu_switch_paths.py and tests/test_gpu_k_rotation.py.  The environment variables of the same names are read ONCE, at the first call into the
  * library; this call changes a switch afterwards.
  * Threading: the switches live in an immutable snapshot; pq_set_option publishes a modified copy with one atomic pointer
  * swap, and every other entry point pins the snapshot that is live when it is ENTERED and plans and launches under that
@@ -205,7 +206,7 @@ int32_t pq_qlinear_s8_kslabs(const int8_t* a, int64_t lda, int64_t slab_stride, 
  *  - K a multiple of 128, ldx and ldw multiples of 16 (the modules pad K with zeros, as for pq_qlinear_s8's fast tiles), xq and wq 16-byte aligned, 1 <= E <= 1024.
  *    M_total == 0 (or N == 0) is a no-op.  No workspace.
  * Tiles: 64(m) x 128(n) or 64 x 64 loader / consumer ring tiles, chosen from the upper bound ceil(M_total / 64) + E of the m-tiles, N and the device's CU count
- * (pq_grouped_variant_name; PQ_GROUPED_TILE = 64x128 | 64x64 forces one, PQ_GROUPED_ROT=1 rotates the K walk between the m-tiles of one expert — time only, never bits). */
+ * (pq_grouped_variant_name; PQ_GROUPED_TILE = 64x128 | 64x64 forces one, PQ_GROUPED_ROT=1 rotates the K walk between the m-tiles of one expert — time only, never bits: tests/test_gpu_grouped_edges.py). */
 int32_t pq_qlinear_s8_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs,
                               const int8_t* wq, int64_t ldw, int64_t w_expert_stride, const float* ws, const void* bias,
                               const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,

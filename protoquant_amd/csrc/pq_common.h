@@ -17,6 +17,8 @@ typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- behaviour switches (host side)
+// ("time only, never bits" below is held by tests/test_gpu_k_rotation.py, tests/test_gpu_switch_paths.py and tests/test_gpu_grouped_edges.py; a switch that no GPU test names
+// fails tests/test_switch_coverage.py)
 // Every switch of the library lives in ONE immutable snapshot.  pq_set_option() (and the one-time pass over the environment) builds a modified
 // copy and publishes it with one atomic pointer swap; every C-ABI entry point pins the snapshot that is live when it is entered (thread-local,
 // pq_api.hip: CallScope) and the planners and launchers of that call read nothing else — so a call plans and launches under ONE consistent set of
@@ -53,7 +55,7 @@ struct Options {
     int silu_tpr = 0;                // 0 auto; 256 forces the 256-thread layout on wide rows
     int rms_wave_max = 256;
     int grouped_tile = 0;            // PQ_GROUPED_TILE: tile of the grouped GEMM (gemm_s8_grouped.hip): 0 = by plan, 1 = "64x128", 2 = "64x64" (tests, experiments)
-    bool grouped_rot = false;        // PQ_GROUPED_ROT=1: K rotation between the m-tiles of one expert that share a weight panel (time only, never bits; off until measured)
+    bool grouped_rot = false;        // PQ_GROUPED_ROT=1: K rotation between the m-tiles of one expert that share a weight panel (time only, never bits: tests/test_gpu_grouped_edges.py; off until measured)
     int (*roctx_push)(const char*) = nullptr;      // PQ_ROCTX=1 (environment only)
     int (*roctx_pop)() = nullptr;
 };
