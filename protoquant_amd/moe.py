@@ -7,7 +7,10 @@ moe_combine      out[t] = sum of the token's k expert rows times their routing w
 MoEGatedMLP      forward(hidden[T, H], topk_ids[T, k], topk_weights[T, k]): quantise once -> moe_route (which also puts the row scales in grouped order) -> grouped
                  gate+up GEMM reading the codes through the row index -> silu_mul_quantize -> grouped down GEMM -> moe_combine: library launches only, no torch
                  kernel in between but the cast of the weights (and the zero-tailed copy of the codes where in_features is not a multiple of 128)
-swap_moe_experts replaces blocks shaped like Mixtral's / Qwen-MoE's sparse MoE block (a ModuleList `experts` of gated MLPs + a router `gate`)
+swap_moe_experts replaces the routed experts of a decoder's sparse MoE blocks, in either layout model code holds them in: an `experts` module with two stacked
+                 parameters gate_up_proj [E, 2 I, H] / down_proj [E, H, I] called as experts(hidden, top_k_index, top_k_weights) (fused_experts_parts: only that module is
+                 replaced, by MoEGatedMLP — router, shared experts and the block's return type stay the model's), or a ModuleList `experts` of gated MLPs next to a
+                 Linear router `gate` (moe_block_parts: the block is replaced by MoEBlock)
 
 route_plan and combine are the same two steps as pure tensor code that runs on any device: the DEFINITION moe_route and moe_combine are held to, element for element and
 bit for bit (tests/test_gpu_moe_route.py, tests/test_gpu_moe_combine.py), and what MoEGatedMLP runs with torch_plumbing = True (A/B: tools/moe_layer_bench.py).  The expert
@@ -15,11 +18,14 @@ SELECTION — router GEMM, softmax, top-k, renormalisation — stays the model's
 Nothing here reads a routing result on the host: the forward is capturable into a hipGraph and replayable for other routings."""
 from __future__ import annotations
 
+import inspect
+from typing import NamedTuple
+
 import torch
 from torch import nn
 
 from . import _lib as L
-from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, qlinear, qlinear_s8_grouped
+from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8_grouped
 from .qtensor import QTensor, quantize, silu_mul_quantize
 
 
@@ -202,6 +208,16 @@ class MoEGatedMLP(nn.Module):
         mlps = [e if isinstance(e, GatedMLP) else GatedMLP.from_linears(*e) for e in experts]
         return cls(GroupedQLinear.from_linears([m.gate_up for m in mlps]), GroupedQLinear.from_linears([m.down for m in mlps]))
 
+    @classmethod
+    def from_stacked(cls, gate_up_proj: torch.Tensor, down_proj: torch.Tensor) -> "MoEGatedMLP":
+        """The experts as model code holds them since transformers 5: gate_up_proj [E, 2 I, H] (per expert the gate rows, then the up rows; y = x @ W[e].T) and
+        down_proj [E, H, I], float, on the GPU.  Every row is quantised per output channel (GroupedQLinear.from_weight): the codes and scales from_experts gives for
+        the E (gate, up, down) slices taken as nn.Linear layers."""
+        if gate_up_proj.dim() != 3 or down_proj.dim() != 3 or gate_up_proj.shape[0] != down_proj.shape[0] or gate_up_proj.shape[2] != down_proj.shape[1] or \
+                gate_up_proj.shape[1] != 2 * down_proj.shape[2]:
+            raise ValueError(f"MoEGatedMLP.from_stacked: expected gate_up_proj [E, 2 I, H] and down_proj [E, H, I], got {tuple(gate_up_proj.shape)} and {tuple(down_proj.shape)}")
+        return cls(GroupedQLinear.from_weight(gate_up_proj), GroupedQLinear.from_weight(down_proj))
+
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         H = hidden.shape[-1]
         x2 = hidden.reshape(-1, H)
@@ -249,7 +265,7 @@ def _expert_linears(mod: nn.Module):
     """(gate, up, down) of a gated expert MLP with a silu — Llama-style names or Mixtral's w1 / w3 / w2 — or None"""
     for names in _EXPERT_NAMES:
         g, u, d = (getattr(mod, n, None) for n in names)
-        if all(isinstance(l, nn.Linear) for l in (g, u, d)):
+        if all(is_plain_linear(l) for l in (g, u, d)):
             if not _is_silu(getattr(mod, "act_fn", None)) or len(list(mod.children())) > 4:
                 return None
             if g.in_features != u.in_features or g.out_features != u.out_features or d.in_features != g.out_features or d.out_features != g.in_features:
@@ -265,7 +281,7 @@ def moe_block_parts(mod: nn.Module):
     output per expert, and a top-k count among its attributes — as (experts' linears, top_k, renormalise, return_router_logits); else None.  Recognised by shape,
     not by import (no dependency on transformers)."""
     experts, gate = getattr(mod, "experts", None), getattr(mod, "gate", None)
-    if not isinstance(experts, nn.ModuleList) or len(experts) == 0 or not isinstance(gate, nn.Linear) or gate.out_features != len(experts):
+    if not isinstance(experts, nn.ModuleList) or len(experts) == 0 or not is_plain_linear(gate) or gate.out_features != len(experts):
         return None
     if {n for n, _ in mod.named_children()} != {"experts", "gate"}:
         return None                                   # (shared experts, gates on the shared path, ...: not this block)
@@ -284,16 +300,80 @@ def moe_block_parts(mod: nn.Module):
     return lins, top_k, renorm, returns_logits
 
 
+class FusedExperts(NamedTuple):
+    """What fused_experts_parts reports of an experts module it recognises.  Only ONE layout is recognised, so the last three fields are fixed by it — no bias, gate rows
+    first; a module with biases or another order is refused, not reported with other values.  They are spelled out because they are what the caller relies on
+    (prepare_for_int8 sizes the receiving module from them) and what tests/test_moe_model_recognition.py checks against the module's own forward."""
+    num_experts: int
+    hidden: int
+    intermediate: int
+    gate_up_bias: bool
+    down_bias: bool
+    gate_first: bool          # rows 0 .. I - 1 of gate_up_proj[e] are the gate (the argument of the silu), rows I .. 2 I - 1 the up projection
+
+
+_FUSED_FLAGS = (("has_gate", True), ("has_bias", False), ("is_transposed", False), ("is_concatenated", True))
+
+
+def fused_experts_parts(mod: nn.Module):
+    """A module that holds the routed experts of a sparse MoE block as two stacked parameters and is called as mod(hidden[T, H], top_k_index[T, k], top_k_weights[T, k])
+    — transformers 5's MixtralExperts, Qwen2MoeExperts / Qwen3MoeExperts, OlmoeExperts, DeepseekV3Experts, PhimoeExperts, GraniteMoeExperts — as FusedExperts; else None.
+    (Refused among the classes of transformers 5.15: GptOssExperts, DeepseekV4Experts, and every other class with a gate, a bias or a storage order of its own.)
+    MoEGatedMLP.forward has that signature and that arithmetic, so such a module is replaced alone: whatever produces the indices and the weights (softmax or sigmoid,
+    grouped top-k, sparsemixer), shared experts and the block's return value stay the model's code.  Recognised by shape and attributes, not by import.  Every part of
+    the module's arithmetic must be the library's, so anything else about it refuses it:
+      * parameters other than gate_up_proj [E, 2 I, H] and down_proj [E, H, I] (biases: GPT-OSS), buffers, child modules other than the activation
+      * an act_fn that is missing or not a silu (GPT-OSS has none: its clamped alpha-sigmoid gate is a method), a gate_up_proj stored [E, H, 2 I] or with interleaved gate /
+        up columns: where the two shapes coincide (H = 2 I) the flags the model code sets on its experts classes decide (is_transposed, is_concatenated, has_bias, has_gate)
+      * a gate of the class's own: transformers routes every gate that is not act_fn(gate) * up through a method `_apply_gate` of the experts class (its decorator
+        installs `_default_apply_gate` where the class has none) — DeepSeek-V4's experts have the shapes, the silu, the flags and the signature of Mixtral's and clamp
+        gate and up to +-swiglu_limit in theirs — so a class whose `_apply_gate` is not that default is refused
+      * a forward whose positional arguments are not (hidden, indices, weights) in that order, judged by substrings of their names.  That last check is a guard against a
+        swapped argument ORDER only; it is no evidence of the arithmetic (GPT-OSS's names pass it).
+    What attributes cannot show — a forward that writes another arithmetic inline — is not detected here."""
+    if isinstance(mod, (nn.ModuleList, MoEGatedMLP)):
+        return None
+    own_gate = getattr(type(mod), "_apply_gate", None)
+    if own_gate is not None and getattr(own_gate, "__name__", "") != "_default_apply_gate":
+        return None
+    params, act = dict(mod.named_parameters(recurse=False)), getattr(mod, "act_fn", None)
+    if set(params) != {"gate_up_proj", "down_proj"} or list(mod.named_buffers(recurse=False)) or not _is_silu(act):
+        return None
+    if any(c is not act for c in mod.children()):
+        return None
+    gu, dn = params["gate_up_proj"], params["down_proj"]
+    if gu.dim() != 3 or dn.dim() != 3 or not gu.is_floating_point() or gu.dtype != dn.dtype:
+        return None
+    E, H, I = gu.shape[0], gu.shape[2], dn.shape[2]
+    if E < 1 or tuple(gu.shape) != (E, 2 * I, H) or tuple(dn.shape) != (E, H, I):
+        return None
+    if any(getattr(mod, flag, want) is not want for flag, want in _FUSED_FLAGS):
+        return None
+    if any(isinstance(getattr(mod, n, E), int) and getattr(mod, n, E) != E for n in ("num_experts", "num_local_experts")):
+        return None
+    try:
+        names = [p.name.lower() for p in inspect.signature(type(mod).forward).parameters.values() if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)][1:]
+    except (TypeError, ValueError):
+        return None
+    if len(names) != 3 or not any(t in names[1] for t in ("ind", "idx", "ids")) or not any(t in names[2] for t in ("weight", "score", "prob")):
+        return None
+    return FusedExperts(E, H, I, False, False, True)
+
+
 def swap_moe_experts(model: nn.Module) -> int:
-    """Replace, in place, every sparse MoE block of the model (moe_block_parts) by MoEBlock: the experts' weights are quantised per output channel and stacked, the
-    router stays what it was.  Returns the number of blocks replaced (0: a dense model is left untouched)."""
+    """Replace, in place, the routed experts of every sparse MoE block of the model: a fused-parameter experts module (fused_experts_parts) by MoEGatedMLP, a block in the
+    ModuleList layout (moe_block_parts) by MoEBlock.  The experts' weights are quantised per output channel, the router stays what it was.  Returns the number of
+    blocks whose experts were replaced (0: a dense model, or a layout that is refused, is left untouched — the very same module objects)."""
     n = 0
     for name, child in list(model.named_children()):
         parts = moe_block_parts(child)
-        if parts is None:
+        if parts is not None:
+            lins, top_k, renorm, returns_logits = parts
+            setattr(model, name, MoEBlock(child.gate, MoEGatedMLP.from_experts(lins), top_k, renorm, returns_logits))
+            n += 1
+        elif fused_experts_parts(child) is not None:
+            setattr(model, name, MoEGatedMLP.from_stacked(child.gate_up_proj.detach(), child.down_proj.detach()))
+            n += 1
+        else:
             n += swap_moe_experts(child)
-            continue
-        lins, top_k, renorm, returns_logits = parts
-        setattr(model, name, MoEBlock(child.gate, MoEGatedMLP.from_experts(lins), top_k, renorm, returns_logits))
-        n += 1
     return n

@@ -544,9 +544,16 @@ def _is_conv1d(mod: nn.Module) -> bool:
             and w.shape[1] == mod.nf and not list(mod.children()))
 
 
+def is_plain_linear(mod: nn.Module) -> bool:
+    """An nn.Linear whose forward IS nn.Linear's.  A subclass that overrides forward computes something else with the same weight — Phi-MoE's router is an nn.Linear
+    whose forward returns (logits, routing weights, selected experts) — and qlinear would replace that forward by y = x W^T + b: such a module is left as it is."""
+    return isinstance(mod, nn.Linear) and type(mod).forward is nn.Linear.forward
+
+
 def swap_linears(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False) -> nn.Module:
     """Replace every nn.Linear (for which predicate(name, module) is true) by qlinear, in place; Hugging Face Conv1D layers (GPT-2: weight stored [K, N]) likewise,
-    through qlinear.from_kn_weight (per-channel quantisation along the strided axis, kernel K2).
+    through qlinear.from_kn_weight (per-channel quantisation along the strided axis, kernel K2).  A subclass of nn.Linear with a forward of its own is not a linear
+    layer to this function (is_plain_linear).
     fuse_gated_mlp=True additionally replaces whole gated-MLP blocks (gate_proj / up_proj / down_proj + SiLU, the
     Llama-family MLP) by GatedMLP: one fused gate+up GEMM, silu*mul fused into the quantisation, the down GEMM."""
     for name, child in list(model.named_children()):
@@ -555,7 +562,7 @@ def swap_linears(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False)
             if fused is not None:
                 setattr(model, name, fused)
                 continue
-        if isinstance(child, nn.Linear) and (predicate is None or predicate(name, child)):
+        if is_plain_linear(child) and (predicate is None or predicate(name, child)):
             setattr(model, name, qlinear.from_linear(child))
         elif _is_conv1d(child) and (predicate is None or predicate(name, child)):
             setattr(model, name, qlinear.from_kn_weight(child.weight, child.bias))      # Hugging Face GPT-2's Conv1D: y = x @ W[K, N] + b

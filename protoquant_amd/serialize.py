@@ -12,7 +12,9 @@ fused projections          ``<parent>.<name>.wq`` = the members' codes concatena
                            quantisation makes the concatenation exact
 gated MLP                  ``<mlp>.gate_up.{wq,ws}`` (gate then up) and ``<mlp>.down.{wq,ws}`` — the GatedMLP layout
 MoE experts                ``<block>.experts.gate_up.{wq,ws}`` int8 ``[E, 2I, H]`` / fp32 ``[E, 2I]`` and ``<block>.experts.down.{wq,ws}``
-                           ``[E, H, I]`` / ``[E, H]`` — the buffers of a block swapped by ``swap_moe_experts`` (its ``state_dict()``)
+                           ``[E, H, I]`` / ``[E, H]`` — the buffers of a block swapped by ``swap_moe_experts`` (its ``state_dict()``).
+                           ``convert_checkpoint(model=...)`` writes them from a checkpoint's stacked ``<block>.experts.gate_up_proj``
+                           ``[E, 2I, H]`` / ``<block>.experts.down_proj`` ``[E, H, I]`` for the experts modules ``fused_experts_parts`` recognises
 column shard (rank r of G) rows ``shard_bounds(N, G, r)`` of ``wq`` / ``ws`` / ``bias`` under ``<mod>.local.*``
 row shard (rank r of G)    columns ``shard_bounds(K, G, r)`` of ``wq``, the FULL-row ``ws``, the bias on rank 0 only, under
                            ``<mod>.local.*``
@@ -30,8 +32,8 @@ from typing import Callable, Iterable
 import torch
 from torch import nn
 
-from .qlinear import FusedQLinear, GatedMLP, _is_silu, qlinear
-from .moe import GroupedQLinear, MoEBlock, MoEGatedMLP, moe_block_parts
+from .qlinear import FusedQLinear, GatedMLP, _is_silu, is_plain_linear, qlinear
+from .moe import GroupedQLinear, MoEBlock, MoEGatedMLP, fused_experts_parts, moe_block_parts
 from .qtensor import quantize
 from .sharded import ColumnShardedQLinear, RowShardedQLinear, ShardedGatedMLP, shard_bounds
 
@@ -58,7 +60,10 @@ def convert_checkpoint(state_dict: dict, *, device="cuda", is_linear: Callable[[
     model: the FLOAT model the checkpoint belongs to (a meta-device instance is enough).  When given, exactly the weights of its
       nn.Linear modules are quantised — the same criterion prepare_for_int8() / swap_linears() use on the loading side — instead of
       the name / shape heuristic `is_linear` (which takes any 2-D float tensor that is not an embedding or a norm: a transposed
-      [in, out] weight such as GPT-2's Conv1D would be quantised along the wrong axis).
+      [in, out] weight such as GPT-2's Conv1D would be quantised along the wrong axis, a router that is a module with a bare
+      `weight` would be quantised at all), and the stacked 3-D parameters of its fused MoE experts modules (fused_experts_parts)
+      are quantised per expert and output channel into ``<experts>.gate_up.*`` / ``<experts>.down.*``.  Without `model` a 3-D
+      parameter is copied through as it is: a state_dict does not say how an experts module lays out or uses it.
 
     fuse: ``{"layers.0.attn.qkv": ["layers.0.attn.q_proj", "layers.0.attn.k_proj", "layers.0.attn.v_proj"]}`` — the members
       are replaced by one FusedQLinear entry.  gated_mlp: prefixes of modules with gate_proj / up_proj / down_proj children
@@ -85,11 +90,27 @@ def convert_checkpoint(state_dict: dict, *, device="cuda", is_linear: Callable[[
                 found = True
         return found
 
+    fused_experts = []
     if model is not None:
-        linear_names = {n for n, m in model.named_modules() if isinstance(m, nn.Linear)}
+        linear_names = {n for n, m in model.named_modules() if is_plain_linear(m)}
         is_linear = lambda name, w: name in linear_names      # noqa: E731
+        fused_experts = [(n, fused_experts_parts(m)) for n, m in model.named_modules() if fused_experts_parts(m) is not None]
     sd = dict(state_dict)
     out = {}
+    for ep, parts in fused_experts:                    # every experts tensor is looked at before anything is quantised
+        E, H, I = parts.num_experts, parts.hidden, parts.intermediate
+        for src, (N, K) in (("gate_up_proj", (2 * I, H)), ("down_proj", (H, I))):
+            w = sd.get(f"{ep}.{src}")
+            if w is None:
+                raise KeyError(f"{ep}.{src}: the model holds fused MoE experts there, the checkpoint has no such tensor")
+            if tuple(w.shape) != (E, N, K):
+                raise ValueError(f"{ep}.{src}: the checkpoint's tensor is {tuple(w.shape)}, the model's experts are [{E}, {N}, {K}]")
+    for ep, _ in fused_experts:
+        for src, dst in (("gate_up_proj", "gate_up"), ("down_proj", "down")):
+            w = sd.pop(f"{ep}.{src}")
+            E, N, K = w.shape
+            wq, ws = _quant_rows(w.reshape(E * N, K), device)
+            out[f"{ep}.{dst}.wq"], out[f"{ep}.{dst}.ws"] = wq.reshape(E, N, K).to(out_device), ws.reshape(E, N).to(out_device)
     lin = {k[:-len(".weight")]: v for k, v in sd.items() if k.endswith(".weight") and is_linear(k[:-len(".weight")], v)}
     used = set()
 
@@ -215,11 +236,18 @@ def empty_sharded_gated_mlp(hidden: int, intermediate: int, world: int, rank: in
 
 
 def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False) -> nn.Module:
-    """The structural half of swap_linears() and swap_moe_experts(): replace every nn.Linear (and, with fuse_gated_mlp, every Llama-style MLP; and every sparse
-    MoE block swap_moe_experts would swap) by an EMPTY int8 module of the same shape — no quantisation, no float weights needed (works on meta-device models) — so that
+    """The structural half of swap_linears() and swap_moe_experts(): replace every nn.Linear (and, with fuse_gated_mlp, every Llama-style MLP; and the routed experts
+    of every sparse MoE block swap_moe_experts would swap, in either layout) by an EMPTY int8 module of the same shape — no quantisation, no float weights needed (works on meta-device models) — so that
     ``model.load_state_dict(convert_checkpoint(...))`` fills it.  Empty buffers live on the linear's device unless it is meta,
     then on the CPU; move the model to the GPU after loading."""
     for name, child in list(model.named_children()):
+        fused = fused_experts_parts(child) if (predicate is None or predicate(name, child)) else None
+        if fused is not None:
+            # fused-parameter experts (transformers 5): only that module is replaced, as swap_moe_experts does — EMPTY stacked experts of the same shape
+            p = child.gate_up_proj
+            setattr(model, name, empty_moe_gated_mlp(fused.num_experts, fused.hidden, fused.intermediate, fused.gate_up_bias, fused.down_bias, p.dtype,
+                                                     None if p.device.type == "meta" else p.device))
+            continue
         moe = moe_block_parts(child) if (predicate is None or predicate(name, child)) else None
         if moe is not None:
             # a block swap_moe_experts would swap: the same wrapper around EMPTY stacked experts (the router stays a float nn.Linear, as swap_moe_experts leaves it),
@@ -239,7 +267,7 @@ def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = Fa
                                empty_qlinear(d.in_features, d.out_features, d.bias is not None, d.weight.dtype, dev))
                 setattr(model, name, mlp)
                 continue
-        if isinstance(child, nn.Linear) and (predicate is None or predicate(name, child)):
+        if is_plain_linear(child) and (predicate is None or predicate(name, child)):
             dev = None if child.weight.device.type == "meta" else child.weight.device
             setattr(model, name, empty_qlinear(child.in_features, child.out_features, child.bias is not None, child.weight.dtype, dev))
         else:
