@@ -52,7 +52,7 @@ const char* pq_last_error(void);
  * the layout pass), PQ_NO_TAILSPLIT, PQ_NO_SPLITK, PQ_FORCE_SPLITK (slice count: experiments), PQ_FSK (0 = no fused
  * split-K, S = S slices), PQ_FSK_SYMMETRIC and PQ_FSK_FENCED (see pq_qlinear_s8), PQ_NO_MIDM (no 64-row ring tiles), PQ_RING_ROT (0 = no K rotation), PQ_FAKE_CUS (plan as if the device had n CUs),
  * PQ_SKINNY_RB ("" = off / auto), PQ_EPI_ANY_ALIGN (0 = the staged epilogue only for 16-byte aligned output rows; default: any element-aligned row),
- * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes), PQ_GROUPED_TILE / PQ_GROUPED_ROT (see pq_qlinear_s8_grouped).  The switches that change launch geometry or pick another kernel for the same result are checked bit for bit in
+ * PQ_K2_BLOCKS_A / PQ_K2_BLOCKS_E (workgroup-count targets of K2's two passes), PQ_GROUPED_TILE / PQ_GROUPED_ROT (see pq_qlinear_s8_grouped), PQ_GROUPED_STREAM_KS / PQ_GROUPED_STREAM_RB (see pq_qlinear_s8_grouped_stream).  The switches that change launch geometry or pick another kernel for the same result are checked bit for bit in
  * tests/test_gpu_switch_paths.py and tests/test_gpu_k_rotation.py.  The environment variables of the same names are read ONCE, at the first call into the
  * library; this call changes a switch afterwards.
  * Threading: the switches live in an immutable snapshot; pq_set_option publishes a modified copy with one atomic pointer
@@ -218,6 +218,25 @@ int32_t pq_gemm_s8s8s32_grouped(const int8_t* xq, int64_t ldx, const int32_t* a_
                                 int32_t* acc, int64_t ldacc, void* stream);
 /* "grouped64x128_16x16x64" | "grouped64x64_16x16x64": the tile the grouped launch would use (static string). */
 const char* pq_grouped_variant_name(int32_t E, int64_t M_total, int64_t N, int64_t K);
+
+/* The grouped qlinear AT DECODE — at most 64 grouped rows (gemm_s8_grouped_stream.hip): the contract, operands and bits of pq_qlinear_s8_grouped above, restricted to
+ * M_total <= 64 (more is PQ_ERR_BAD_ARG, before any HIP call), served by the weight-streaming kernel instead of a 64-row tile: ceil(N / 16 RB) weight blocks x
+ * min(E, M_total) expert slots are launched, slot j finds the j-th expert that owns a row from `offsets` on the device, KS waves per workgroup split K and stream that
+ * expert's weight rows straight into MFMA operands — the weights of a live expert are read once, an expert without a row costs nothing but its slot's early exit.  No
+ * workspace, no atomics, no wait between workgroups; graph-capturable, a replay is right when only the contents of offsets / a_row_index / xs change.  Entry points of
+ * their own: pq_qlinear_s8_grouped and pq_grouped_variant_name keep planning the tile kernels at every M_total.
+ * PQ_GROUPED_STREAM_KS (waves per workgroup: a power of two <= 16) and PQ_GROUPED_STREAM_RB (1 | 2 weight blocks per wave; 2 only while M_total <= 32) force the plan —
+ * time only, never bits: tests/test_gpu_grouped_stream.py. */
+int32_t pq_qlinear_s8_grouped_stream(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs,
+                                     const int8_t* wq, int64_t ldw, int64_t w_expert_stride, const float* ws, const void* bias,
+                                     const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                                     void* y, int64_t ldy, int32_t out_dtype, void* stream);
+int32_t pq_gemm_s8s8s32_grouped_stream(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows,
+                                       const int8_t* wq, int64_t ldw, int64_t w_expert_stride,
+                                       const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                                       int32_t* acc, int64_t ldacc, void* stream);
+/* "gstream_mt<1|2|4>_rb<1|2>_ks<1..16>_16x16x64": token tiles the kernel is compiled for, weight blocks per wave and waves per workgroup of that launch (static string). */
+const char* pq_grouped_stream_plan_name(int32_t E, int64_t M_total, int64_t N, int64_t K);
 
 /* ROUTING of a mixture-of-experts layer (moe_kernels.hip, kernel R): the (token, slot) pairs of topk_ids[T, k] sorted by expert — a STABLE counting sort of the flat pairs
  * p = t * k + j by topk_ids[t][j].  All outputs int32, in device memory:

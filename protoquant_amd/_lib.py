@@ -23,6 +23,7 @@ EXPORTS = (
     "pq_silu_mul_rowamax", "pq_silu_mul_quant_rowwise_amax", "pq_qlinear_s8_kslabs", "pq_qlinear_kslabs_workspace_bytes", "pq_qlinear_kslabs_workspace_bytes_for", "pq_kslabs_way_name",
     "pq_quant_rowamax", "pq_quant_rowwise_amax",
     "pq_qlinear_s8_grouped", "pq_gemm_s8s8s32_grouped", "pq_grouped_variant_name",
+    "pq_qlinear_s8_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", "pq_grouped_stream_plan_name",
     "pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine",
 )
 
@@ -90,6 +91,12 @@ def lib() -> ctypes.CDLL:
     L.pq_gemm_s8s8s32_grouped.argtypes = [vp, i64, vp, i64, vp, i64, i64, vp, i32, i64, i64, i64, vp, i64, vp]
     L.pq_grouped_variant_name.restype = ctypes.c_char_p
     L.pq_grouped_variant_name.argtypes = [i32, i64, i64, i64]
+    L.pq_qlinear_s8_grouped_stream.restype = i32
+    L.pq_qlinear_s8_grouped_stream.argtypes = L.pq_qlinear_s8_grouped.argtypes
+    L.pq_gemm_s8s8s32_grouped_stream.restype = i32
+    L.pq_gemm_s8s8s32_grouped_stream.argtypes = L.pq_gemm_s8s8s32_grouped.argtypes
+    L.pq_grouped_stream_plan_name.restype = ctypes.c_char_p
+    L.pq_grouped_stream_plan_name.argtypes = [i32, i64, i64, i64]
     L.pq_moe_route_workspace_bytes.restype = sz
     L.pq_moe_route_workspace_bytes.argtypes = [i64, i32, i32]
     L.pq_moe_route.restype = i32

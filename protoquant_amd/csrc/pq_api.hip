@@ -23,6 +23,9 @@ template <int OUT> void launch_gemm_ring128(const int8_t*, int64_t, const int8_t
 template <int OUT> void launch_gemm_ringt(int, const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t, int64_t a_slab_stride = 0, int64_t a_k_per_slab = 0);
 template <int OUT> void launch_gemm_skinny(const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t);
 template <int OUT> void launch_gemm_grouped(int, const int8_t*, int64_t, const int32_t*, int64_t, const int8_t*, int64_t, int64_t, const EpiArgs&, const int32_t*, int, int64_t, int64_t, int64_t, int, hipStream_t);
+template <int OUT> void launch_gemm_grouped_stream(const int8_t*, int64_t, const int32_t*, int64_t, const int8_t*, int64_t, int64_t, const EpiArgs&, const int32_t*, int, int64_t, int64_t, int64_t, hipStream_t);
+void grouped_stream_plan(int32_t, int64_t, int64_t, int64_t, int*, int*, int*);
+const char* grouped_stream_plan_name(int, int, int);
 bool gemm_fast_eligible(const int8_t*, int64_t, const int8_t*, int64_t, int64_t, int64_t, int64_t);
 size_t moe_route_workspace_bytes(int64_t npairs, int E);
 void launch_moe_route(const void*, bool, int64_t, int64_t, int, int, int32_t*, int32_t*, int32_t*, int32_t*, const float*, float*, void*, hipStream_t);
@@ -84,7 +87,7 @@ thread_local int tl_depth = 0;
 
 // every behaviour switch, by name: the ONE place both the environment pass (once) and pq_set_option go through
 const char* const kOptionNames[] = {"PQ_FORCE_VARIANT", "PQ_NO_TAILSPLIT", "PQ_NO_SPLITK", "PQ_FORCE_SPLITK", "PQ_FSK", "PQ_FSK_SYMMETRIC", "PQ_FSK_FENCED", "PQ_FSK_COOP", "PQ_FAKE_CUS", "PQ_NO_MIDM", "PQ_NO_KSLABS", "PQ_NO_RING160", "PQ_MIDM_CT", "PQ_RMS_WAVE_MAX", "PQ_SILU_TPR", "PQ_SP128_LC",
-                                    "PQ_SP256_P3", "PQ_SP256_ASM", "PQ_SP256_PERSIST", "PQ_RING_LC", "PQ_RING_ROT", "PQ_K1_LDS", "PQ_EPI_ANY_ALIGN", "PQ_K2_BLOCKS_A", "PQ_K2_BLOCKS_E", "PQ_K1_RPW", "PQ_K1_ST16", "PQ_SKINNY_RB", "PQ_SKINNY_STAGE", "PQ_SKINNY_KS", "PQ_GROUPED_TILE", "PQ_GROUPED_ROT"};
+                                    "PQ_SP256_P3", "PQ_SP256_ASM", "PQ_SP256_PERSIST", "PQ_RING_LC", "PQ_RING_ROT", "PQ_K1_LDS", "PQ_EPI_ANY_ALIGN", "PQ_K2_BLOCKS_A", "PQ_K2_BLOCKS_E", "PQ_K1_RPW", "PQ_K1_ST16", "PQ_SKINNY_RB", "PQ_SKINNY_STAGE", "PQ_SKINNY_KS", "PQ_GROUPED_TILE", "PQ_GROUPED_ROT", "PQ_GROUPED_STREAM_KS", "PQ_GROUPED_STREAM_RB"};
 bool apply_option(pq::Options& o, const char* name, const char* value) {
     const bool set = value && *value;
     const int iv = set ? atoi(value) : 0;
@@ -120,6 +123,8 @@ bool apply_option(pq::Options& o, const char* name, const char* value) {
     else if (!strcmp(name, "PQ_SKINNY_RB")) o.skinny_rb = set && *value == '2' ? 2 : (set && *value == '1' ? 1 : 0);
     else if (!strcmp(name, "PQ_GROUPED_TILE")) o.grouped_tile = !set ? 0 : (!strcmp(value, "64x128") ? 1 : (!strcmp(value, "64x64") ? 2 : 0));
     else if (!strcmp(name, "PQ_GROUPED_ROT")) o.grouped_rot = set && *value == '1';
+    else if (!strcmp(name, "PQ_GROUPED_STREAM_KS")) o.grouped_stream_ks = iv > 0 ? iv : 0;
+    else if (!strcmp(name, "PQ_GROUPED_STREAM_RB")) o.grouped_stream_rb = set && *value == '2' ? 2 : (set && *value == '1' ? 1 : 0);
     else return false;
     return true;
 }
@@ -872,6 +877,50 @@ const char* pq_grouped_variant_name(int32_t E, int64_t M_total, int64_t N, int64
     CallScope scope_;
     (void)K;      // (both tiles step through K in the same 128-byte K-tiles)
     return grouped_plan(E, M_total, N) == 0 ? "grouped64x128_16x16x64" : "grouped64x64_16x16x64";
+}
+
+// ---- the grouped GEMM at decode: at most 64 grouped rows, the live experts' weights streamed once (gemm_s8_grouped_stream.hip).  Entry points of their own: the planner
+// of pq_qlinear_s8_grouped and pq_grouped_variant_name keep answering for the tile kernels at every M_total.
+static int32_t grouped_stream_rows_check(const char* what, int64_t M_total) {
+    if (M_total > 64) return fail(PQ_ERR_BAD_ARG, "%s: M_total = %lld (the weight-streaming grouped kernel serves at most 64 grouped rows; use pq_qlinear_s8_grouped)", what, (long long)M_total);
+    return PQ_OK;
+}
+
+int32_t pq_qlinear_s8_grouped_stream(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs, const int8_t* wq, int64_t ldw,
+                                     int64_t w_expert_stride, const float* ws, const void* bias, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K,
+                                     void* y, int64_t ldy, int32_t out_dtype, void* stream) {
+    Range range_("pq:qlinear_s8_grouped_stream (K3+K4)");
+    if (out_dtype < 0 || out_dtype > 2) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_s8_grouped_stream: unknown out_dtype %d", out_dtype);
+    if (const int32_t st = grouped_check("pq_qlinear_s8_grouped_stream", xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, offsets, E, M_total, N, K, y, ldy)) return st;
+    if (const int32_t st = grouped_stream_rows_check("pq_qlinear_s8_grouped_stream", M_total)) return st;
+    if (M_total > 0 && N > 0 && (!xs || !ws)) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_s8_grouped_stream: %s is null", !xs ? "xs" : "ws");
+    if (M_total == 0 || N == 0) return PQ_OK;
+    pq::EpiArgs epi{xs, ws, bias, y, ldy, 0};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (out_dtype) {
+        case PQ_BF16: pq::launch_gemm_grouped_stream<PQ_BF16>(xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, st); break;
+        case PQ_FP16: pq::launch_gemm_grouped_stream<PQ_FP16>(xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, st); break;
+        default: pq::launch_gemm_grouped_stream<PQ_F32>(xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, st); break;
+    }
+    return check_launch("pq_qlinear_s8_grouped_stream");
+}
+
+int32_t pq_gemm_s8s8s32_grouped_stream(const int8_t* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const int8_t* wq, int64_t ldw, int64_t w_expert_stride,
+                                       const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t K, int32_t* acc, int64_t ldacc, void* stream) {
+    Range range_("pq:gemm_s8s8s32_grouped_stream (K3)");
+    if (const int32_t st = grouped_check("pq_gemm_s8s8s32_grouped_stream", xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, offsets, E, M_total, N, K, acc, ldacc)) return st;
+    if (const int32_t st = grouped_stream_rows_check("pq_gemm_s8s8s32_grouped_stream", M_total)) return st;
+    if (M_total == 0 || N == 0) return PQ_OK;
+    pq::EpiArgs epi{nullptr, nullptr, nullptr, acc, ldacc, 0};
+    pq::launch_gemm_grouped_stream<pq::OUT_I32>(xq, ldx, a_row_index, x_rows, wq, ldw, w_expert_stride, epi, offsets, E, M_total, N, K, static_cast<hipStream_t>(stream));
+    return check_launch("pq_gemm_s8s8s32_grouped_stream");
+}
+
+const char* pq_grouped_stream_plan_name(int32_t E, int64_t M_total, int64_t N, int64_t K) {
+    CallScope scope_;
+    int mt = 1, rb = 1, ks = 1;
+    pq::grouped_stream_plan(E < 1 ? 1 : E, M_total < 0 ? 0 : (M_total > 64 ? 64 : M_total), N < 0 ? 0 : N, K < 64 ? 64 : K, &mt, &rb, &ks);
+    return pq::grouped_stream_plan_name(mt, rb, ks);
 }
 
 // ---- routing and combine of a mixture-of-experts layer (moe_kernels.hip): every argument is checked, and the failing one named, before any HIP call

@@ -17,7 +17,7 @@ typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- behaviour switches (host side)
-// ("time only, never bits" below is held by tests/test_gpu_k_rotation.py, tests/test_gpu_switch_paths.py and tests/test_gpu_grouped_edges.py; a switch that no GPU test names
+// ("time only, never bits" below is held by tests/test_gpu_k_rotation.py, tests/test_gpu_switch_paths.py, tests/test_gpu_grouped_edges.py and tests/test_gpu_grouped_stream.py; a switch that no GPU test names
 // fails tests/test_switch_coverage.py)
 // Every switch of the library lives in ONE immutable snapshot.  pq_set_option() (and the one-time pass over the environment) builds a modified
 // copy and publishes it with one atomic pointer swap; every C-ABI entry point pins the snapshot that is live when it is entered (thread-local,
@@ -56,6 +56,8 @@ struct Options {
     int rms_wave_max = 256;
     int grouped_tile = 0;            // PQ_GROUPED_TILE: tile of the grouped GEMM (gemm_s8_grouped.hip): 0 = by plan, 1 = "64x128", 2 = "64x64" (tests, experiments)
     bool grouped_rot = false;        // PQ_GROUPED_ROT=1: K rotation between the m-tiles of one expert that share a weight panel (time only, never bits: tests/test_gpu_grouped_edges.py; off until measured)
+    int grouped_stream_rb = 0;       // PQ_GROUPED_STREAM_RB: weight blocks per wave of the grouped weight-streaming kernel (gemm_s8_grouped_stream.hip): 0 by plan, 1 / 2 forced (time only, never bits: tests/test_gpu_grouped_stream.py)
+    int grouped_stream_ks = 0;       // PQ_GROUPED_STREAM_KS: its forced K split (waves per workgroup, a power of two <= 16); 0 by plan (time only, never bits: same file)
     int (*roctx_push)(const char*) = nullptr;      // PQ_ROCTX=1 (environment only)
     int (*roctx_pop)() = nullptr;
 };

@@ -25,13 +25,23 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8_grouped
+from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8_grouped, qlinear_s8_grouped_stream
 from .qtensor import QTensor, quantize, silu_mul_quantize
+
+
+# Grouped rows up to which GroupedQLinear.forward takes the weight-streaming grouped kernel.  From profiles/r11_moe_decode_bench.txt: the largest of 64 / 32 / 16 / 0 at which
+# no recorded row is more than 3 % slower than the tile path.
+STREAM_ROWS_DEFAULT = 64
 
 
 class GroupedQLinear(_KPadded, nn.Module):
     """E linear layers of one shape held together: wq int8 [E, N, K], ws f32 [E, N], bias [E, N] or None.  in_features that is not a multiple of 128 is served as in
-    qlinear (_KPadded): a zero-padded copy of the weight, made lazily, and zero-tailed activation codes — same bits."""
+    qlinear (_KPadded): a zero-padded copy of the weight, made lazily, and zero-tailed activation codes — same bits.
+    stream_rows (class attribute, settable per instance): a forward with 0 < M_total <= stream_rows grouped rows — a decode step — goes through the weight-streaming
+    grouped kernel (qlinear_s8_grouped_stream), any other through the 64-row tiles (qlinear_s8_grouped); same bits either way.  M_total is a shape, known on the host:
+    nothing synchronises and a captured step keeps its path.  0 = always the tiles; at most 64."""
+
+    stream_rows = STREAM_ROWS_DEFAULT
 
     def __init__(self, num_experts: int, in_features: int, out_features: int, bias: bool = False, device=None, dtype=None):
         super().__init__()
@@ -100,10 +110,13 @@ class GroupedQLinear(_KPadded, nn.Module):
         if xs is None:
             xs = xq.scale if row_index is None else xq.scale.index_select(0, row_index)
         wq, _ = self._wq_for_gemm()
-        return qlinear_s8_grouped(codes, xs, wq, self.ws, self.bias, offsets, xq.orig_dtype, row_index=row_index)
+        M_total = codes.shape[0] if row_index is None else row_index.numel()
+        grouped = qlinear_s8_grouped_stream if 0 < M_total <= self.stream_rows else qlinear_s8_grouped
+        return grouped(codes, xs, wq, self.ws, self.bias, offsets, xq.orig_dtype, row_index=row_index)
 
     def extra_repr(self):
-        return f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+        return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
+                f"stream_rows={self.stream_rows}")
 
 
 def route_plan(topk_ids: torch.Tensor, num_experts: int):

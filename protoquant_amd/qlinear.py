@@ -225,14 +225,11 @@ def _grouped_operands(what: str, xq, wq, offsets, row_index):
     return xq, wq, E, N, K, M_total
 
 
-def qlinear_s8_grouped(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, offsets: torch.Tensor, out_dtype,
-                       row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
-    """The fused int8 GEMM + dequant epilogue over ALL experts of a mixture-of-experts layer in one launch (C-ABI pq_qlinear_s8_grouped): the rows are a token list sorted by
-    expert, rows offsets[e] .. offsets[e + 1] - 1 (int32 [E + 1], on the device — it is never read on the host) go through expert e's weight wq[e] ([E, N, K] int8),
-    scales ws[e] ([E, N]) and bias[e].  row_index (int32 [M_total], optional): row r reads its codes from row row_index[r] of xq, the un-permuted [T, K] code matrix;
-    without it xq is already in grouped order.  xs [M_total] is always in grouped order.  Every row has the bits of qlinear_s8 run per expert on its row slice; rows
-    >= offsets[E] of the output are left untouched."""
-    xq, wq, E, N, K, M = _grouped_operands("qlinear_s8_grouped", xq, wq, offsets, row_index)
+def _qlinear_s8_grouped(what: str, max_rows, xq, xs, wq, ws, bias, offsets, out_dtype, row_index, out):
+    """qlinear_s8_grouped / qlinear_s8_grouped_stream: one set of operand checks, then the C-ABI entry point pq_<what>"""
+    xq, wq, E, N, K, M = _grouped_operands(what, xq, wq, offsets, row_index)
+    if max_rows is not None and M > max_rows:
+        raise ValueError(f"{what}: at most {max_rows} grouped rows, got {M} (qlinear_s8_grouped takes any number)")
     dev = xq.device
     code = L.dtype_code(out_dtype)
     _check_operand(xs, "xs", dev, torch.float32, M)
@@ -251,16 +248,17 @@ def qlinear_s8_grouped(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws:
             raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
     y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
     with torch.cuda.device(dev):
-        L.check(L.lib().pq_qlinear_s8_grouped(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0], xs.data_ptr(),
-                                              wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K), ws.data_ptr(),
-                                              bias.data_ptr() if bias is not None else None, offsets.data_ptr(), E, M, N, K, y.data_ptr(), L.ld(y), code,
-                                              L.stream_ptr(xq)), "qlinear_s8_grouped")
+        L.check(getattr(L.lib(), "pq_" + what)(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0], xs.data_ptr(),
+                                               wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K), ws.data_ptr(),
+                                               bias.data_ptr() if bias is not None else None, offsets.data_ptr(), E, M, N, K, y.data_ptr(), L.ld(y), code,
+                                               L.stream_ptr(xq)), what)
     return y
 
 
-def int_mm_grouped(xq: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
-    """The exact int32 accumulators of qlinear_s8_grouped (C-ABI pq_gemm_s8s8s32_grouped): acc[r] = xq[src(r)] . wq[e(r)]^T — int_mm per expert, in one launch."""
-    xq, wq, E, N, K, M = _grouped_operands("int_mm_grouped", xq, wq, offsets, row_index)
+def _int_mm_grouped(what: str, entry: str, max_rows, xq, wq, offsets, row_index, out):
+    xq, wq, E, N, K, M = _grouped_operands(what, xq, wq, offsets, row_index)
+    if max_rows is not None and M > max_rows:
+        raise ValueError(f"{what}: at most {max_rows} grouped rows, got {M} (int_mm_grouped takes any number)")
     dev = xq.device
     if out is not None:
         _check_operand(out, "out", dev, torch.int32)
@@ -268,10 +266,41 @@ def int_mm_grouped(xq: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, ro
             raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
     acc = out if out is not None else torch.empty((M, N), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        L.check(L.lib().pq_gemm_s8s8s32_grouped(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0],
-                                                wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K),
-                                                offsets.data_ptr(), E, M, N, K, acc.data_ptr(), L.ld(acc), L.stream_ptr(xq)), "int_mm_grouped")
+        L.check(getattr(L.lib(), entry)(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0],
+                                        wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K),
+                                        offsets.data_ptr(), E, M, N, K, acc.data_ptr(), L.ld(acc), L.stream_ptr(xq)), what)
     return acc
+
+
+def qlinear_s8_grouped(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, offsets: torch.Tensor, out_dtype,
+                       row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The fused int8 GEMM + dequant epilogue over ALL experts of a mixture-of-experts layer in one launch (C-ABI pq_qlinear_s8_grouped): the rows are a token list sorted by
+    expert, rows offsets[e] .. offsets[e + 1] - 1 (int32 [E + 1], on the device — it is never read on the host) go through expert e's weight wq[e] ([E, N, K] int8),
+    scales ws[e] ([E, N]) and bias[e].  row_index (int32 [M_total], optional): row r reads its codes from row row_index[r] of xq, the un-permuted [T, K] code matrix;
+    without it xq is already in grouped order.  xs [M_total] is always in grouped order.  Every row has the bits of qlinear_s8 run per expert on its row slice; rows
+    >= offsets[E] of the output are left untouched."""
+    return _qlinear_s8_grouped("qlinear_s8_grouped", None, xq, xs, wq, ws, bias, offsets, out_dtype, row_index, out)
+
+
+def int_mm_grouped(xq: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The exact int32 accumulators of qlinear_s8_grouped (C-ABI pq_gemm_s8s8s32_grouped): acc[r] = xq[src(r)] . wq[e(r)]^T — int_mm per expert, in one launch."""
+    return _int_mm_grouped("int_mm_grouped", "pq_gemm_s8s8s32_grouped", None, xq, wq, offsets, row_index, out)
+
+
+STREAM_ROWS_MAX = 64      # grouped rows the weight-streaming grouped kernel serves (pq_qlinear_s8_grouped_stream refuses more)
+
+
+def qlinear_s8_grouped_stream(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, offsets: torch.Tensor, out_dtype,
+                              row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """qlinear_s8_grouped for DECODE steps — at most 64 grouped rows — through the weight-streaming grouped kernel (C-ABI pq_qlinear_s8_grouped_stream): the same operands,
+    the same checks and the same bits, but every expert that owns a row has its weight streamed once, straight into MFMA operands, by several waves per 16-row block,
+    instead of being staged for a 64-row tile that holds one or two rows.  offsets / row_index stay on the device; more than 64 grouped rows is an error."""
+    return _qlinear_s8_grouped("qlinear_s8_grouped_stream", STREAM_ROWS_MAX, xq, xs, wq, ws, bias, offsets, out_dtype, row_index, out)
+
+
+def int_mm_grouped_stream(xq: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The exact int32 accumulators of qlinear_s8_grouped_stream (C-ABI pq_gemm_s8s8s32_grouped_stream): int_mm_grouped for at most 64 grouped rows."""
+    return _int_mm_grouped("int_mm_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", STREAM_ROWS_MAX, xq, wq, offsets, row_index, out)
 
 
 def qlinear_dyn(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias=None) -> torch.Tensor:

@@ -2,7 +2,9 @@
 pq.qlinear_s8 on the SAME buffers — the gate+up and the down GEMM of one MoE layer, outputs compared bit for bit, both timed from hipGraph replays, interleaved round by
 round.  The graphs walk a rotation of weight sets larger than the 256-MiB Infinity Cache, so the weights come from HBM as they do for a layer inside a model.
 Cases: (a) Mixtral 8 x 7B  E = 8, k = 2, 4096 -> 2 x 14336 -> 4096;  (b) E = 128, k = 8, 2048 -> 2 x 768 -> 2048;  each at T = 4096 (prefill) and T = 32 (decode),
-with balanced, Zipf-skewed and one-expert-takes-all routings (seeded).  usage: python tools/grouped_bench.py [--quick] [--rot]"""
+with balanced, Zipf-skewed and one-expert-takes-all routings (seeded).
+--decode: the two GEMMs alone at T = 1, 8, 32 — the weight-streaming entry (pq.qlinear_s8_grouped_stream) against the tile entry (pq.qlinear_s8_grouped) on the same
+buffers, with the bytes of the live experts' weights and the TB/s they imply.  usage: python tools/grouped_bench.py [--quick] [--rot] [--decode]"""
 import subprocess
 import sys
 import time
@@ -97,7 +99,79 @@ def bench_gemm(tag, E, N, K, M, off_np, rounds):
     return tg, tl
 
 
+def bench_decode_gemm(tag, E, N, K, M, off_np, rounds):
+    """one grouped GEMM at decode size: streaming entry against tile entry, weight sets rotated (HBM-fed); returns (stream us, tiles us)"""
+    live = int((np.diff(off_np) > 0).sum())
+    nrot = max(2, min(16, -(-512 * 2**20 // (live * N * K))))          # the LIVE experts of the rotation: more than the Infinity Cache holds
+    g = torch.Generator(device=dev).manual_seed(N + K + M)
+    wrot = [torch.randint(-127, 128, (E, N, K), generator=g, device=dev, dtype=torch.int8) for _ in range(nrot)]
+    ws = torch.rand(E, N, generator=g, device=dev) * 1e-2 + 1e-3
+    xq = torch.randint(-127, 128, (M, K), generator=g, device=dev, dtype=torch.int8)
+    xs = torch.rand(M, generator=g, device=dev) * 1e-2 + 1e-3
+    off = torch.from_numpy(off_np.astype(np.int32)).to(dev)
+    ys = [torch.empty((M, N), dtype=torch.bfloat16, device=dev) for _ in range(2)]
+    graphs = []
+    for fn, y in ((pq.qlinear_s8_grouped_stream, ys[0]), (pq.qlinear_s8_grouped, ys[1])):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            fn(xq, xs, wrot[0], ws, None, off, torch.bfloat16, out=y)
+        torch.cuda.current_stream().wait_stream(s)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for w in wrot:
+                fn(xq, xs, w, ws, None, off, torch.bfloat16, out=y)
+        graphs.append(gr)
+    for gr in graphs:
+        gr.replay()
+    torch.cuda.synchronize()
+    same = torch.equal(ys[0].view(torch.int16), ys[1].view(torch.int16))
+    ts = [[], []]
+    for _ in range(rounds):
+        for i, gr in enumerate(graphs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            gr.replay()
+            b.record()
+            b.synchronize()
+            ts[i].append(a.elapsed_time(b) * 1e3 / nrot)
+    t_s, t_t = (float(np.median(t)) for t in ts)
+    nbytes = live * N * K
+    plan = _lib.lib().pq_grouped_stream_plan_name(E, M, N, K).decode()
+    print(f"  {tag:<8} M={M:<4} N={N:<6} K={K:<6} streaming {t_s:8.1f} us [{min(ts[0]):.1f} .. {max(ts[0]):.1f}] = {nbytes / t_s / 1e6:5.2f} TB/s   tiles {t_t:8.1f} us "
+          f"[{min(ts[1]):.1f} .. {max(ts[1]):.1f}] = {nbytes / t_t / 1e6:5.2f} TB/s   x{t_t / t_s:5.2f}   {live} live experts = {nbytes / 1e6:.1f} MB ({nrot} weight sets)   {plan}   "
+          f"bits {'SAME' if same else 'DIFFER'}", flush=True)
+    assert same, "the streaming entry differs from the tile entry"
+    del wrot, graphs
+    torch.cuda.empty_cache()
+    return t_s, t_t
+
+
+def decode_main():
+    print(f"# {torch.cuda.get_device_name(0)}; {time.strftime('%Y-%m-%d')}; the two grouped GEMMs of a MoE layer at decode sizes: pq.qlinear_s8_grouped_stream against pq.qlinear_s8_grouped; "
+          "medians [min .. max] of hipGraph replays in turn, weight sets rotated (HBM-fed); TB/s = bytes of the live experts' weights / time")
+    print(f"# clocks before: {sclk()}")
+    rng = np.random.default_rng(0)
+    for (name, E, k, H, inter) in CASES:
+        for T in (1, 8, 32):
+            M = T * k
+            if M > 64:
+                print(f"{name}  T={T} k={k}: {M} grouped rows — beyond the 64 the streaming entry serves; GroupedQLinear takes the tiles there whatever stream_rows says")
+                continue
+            for kind in (("balanced",) if E == 8 else ("balanced", "zipf")):
+                c = np.bincount(rng.choice(E, size=M, replace=M > E), minlength=E) if kind == "balanced" and M <= E else counts_for(kind, E, M, rng)
+                off = np.concatenate([[0], np.cumsum(c)])
+                print(f"{name}  T={T} k={k} routing={kind}  (largest expert {int(c.max())} rows, {int((c > 0).sum())} of {E} experts live)")
+                rounds = 5 if quick else 9
+                s1, t1 = bench_decode_gemm("gate+up", E, 2 * inter, H, M, off, rounds)
+                s2, t2 = bench_decode_gemm("down", E, H, inter, M, off, rounds)
+                print(f"  layer (both GEMMs): streaming {s1 + s2:8.1f} us   tiles {t1 + t2:8.1f} us   x{(t1 + t2) / (s1 + s2):5.2f}")
+    print(f"# clocks after: {sclk()}")
+
+
 def main():
+    if "--decode" in sys.argv:
+        return decode_main()
     print(f"# {torch.cuda.get_device_name(0)}; {time.strftime('%Y-%m-%d')}; PQ_GROUPED_ROT={'1' if '--rot' in sys.argv else '0'}; medians of hipGraph replays, weights rotated (HBM-fed)")
     print(f"# clocks before: {sclk()}")
     rng = np.random.default_rng(0)

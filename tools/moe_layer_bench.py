@@ -4,7 +4,10 @@ Per case also the routing alone and the combine alone, each HIP against torch; t
 rows come from HBM as they do behind a GEMM that has just streamed its weights (at decode sizes the rotation is capped at 12 buffers: those rows are cache-fed, and say so).
 The expert weights need no rotation: one set is 0.6 GB (E = 128) or 1.4 GB (Mixtral).
 Cases: (b) E = 128, k = 8, 2048 -> 2 x 768 -> 2048, balanced and Zipf routing;  (a) Mixtral 8 x 7B  E = 8, k = 2, 4096 -> 2 x 14336 -> 4096;  each at T = 4096, 32 and 1.
-usage: python tools/moe_layer_bench.py [--quick]
+--decode: the decode sizes T = 1, 8, 32 of the same cases — the forward with GroupedQLinear.stream_rows = 64 (the weight-streaming grouped kernel for both GEMMs) against
+stream_rows = 0 (the 64-row tiles), outputs compared bit for bit before timing, the two graphs replayed in turn.  Every forward of a graph has a routing of its own and
+walks a rotation of module copies, so that the live experts' weights of one graph are more than the 256-MiB Infinity Cache holds (printed per row).
+usage: python tools/moe_layer_bench.py [--quick] [--decode]
        python tools/moe_layer_bench.py --one-forward     (under rocprofv3 --kernel-trace: one forward per plumbing between marker kernels)
        python tools/moe_layer_bench.py --list <kernel_trace.csv>      (the kernels between the markers, in launch order)"""
 import csv
@@ -145,6 +148,56 @@ def bench_case(name, E, k, H, inter, kind, T, rounds, dev):
     torch.cuda.empty_cache()
 
 
+def bench_decode(name, E, k, H, inter, kind, T, rounds, dev, mods):
+    """forward at stream_rows 64 against 0; forward i of a graph runs module copy i % len(mods) under routing i"""
+    reps = 12 if E > 8 else 4
+    xs_ = [(torch.randn(T, H, device=dev, generator=torch.Generator(device=dev).manual_seed(i)) * 1.5).to(torch.bfloat16) for i in range(reps)]
+    routes = [routing(kind, T, E, k, 31 * T + i, dev) for i in range(reps)]
+    per_expert = 3 * H * inter                                      # int8 bytes of one expert's gate+up and down
+    live = [int((torch.bincount(ids.reshape(-1), minlength=E) > 0).sum()) for ids, _ in routes]
+    union = [set() for _ in mods]
+    for i, (ids, _) in enumerate(routes):
+        union[i % len(mods)].update(ids.reshape(-1).tolist())
+    distinct = sum(len(u) for u in union) * per_expert
+    mean_bytes = float(np.mean(live)) * per_expert
+
+    def forward(rows):
+        def fn(i):
+            m = mods[i % len(mods)]
+            m.gate_up.stream_rows = m.down.stream_rows = rows
+            return m(xs_[i], *routes[i])
+        return fn
+    (g_s, out_s), (g_t, out_t) = graph_of(forward(64), reps), graph_of(forward(0), reps)
+    g_s.replay(); g_t.replay()
+    torch.cuda.synchronize()
+    same = all(torch.equal(a.view(torch.int16), b.view(torch.int16)) for a, b in zip(out_s, out_t))
+    (ts, slo, shi), (tt, tlo, thi) = time_pair([g_s, g_t], reps, rounds)
+    print(f"{name}  T={T} k={k} routing={kind}  ({np.mean(live):.1f} of {E} experts live per forward = {mean_bytes / 1e6:.0f} MB; {distinct / 2**20:.0f} MiB of distinct live weights per graph "
+          f"of {reps} forwards over {len(mods)} module cop{'y' if len(mods) == 1 else 'ies'})", flush=True)
+    print(f"  forward   stream_rows=64 {ts:9.1f} us [{slo:.1f} .. {shi:.1f}]   stream_rows=0 {tt:9.1f} us [{tlo:.1f} .. {thi:.1f}]   x{tt / ts:5.2f}   "
+          f"weights alone at 5.0 TB/s: {mean_bytes / 5.0e6:.1f} us   bits {'SAME' if same else 'DIFFER'}", flush=True)
+    assert same, "stream_rows 64 and 0 give different outputs"
+    return tt / ts
+
+
+def decode(dev, quick):
+    print(f"# {torch.cuda.get_device_name(0)}; {time.strftime('%Y-%m-%d')}; MoEGatedMLP.forward at decode sizes, medians [min .. max] of hipGraph replays, the two paths replayed in turn; bf16")
+    print(f"# clocks before: {sclk()}")
+    import protoquant_amd as pq
+    worst = {}
+    for (name, E, k, H, inter, kinds) in CASES:
+        mods = [make_moe(E, H, inter, dev) for _ in range(3 if E > 8 else 1)]
+        for kind in kinds:
+            for T in (1, 8, 32):
+                r = bench_decode(name, E, k, H, inter, kind, T, 5 if quick else 11, dev, mods)
+                worst[T * k] = min(worst.get(T * k, r), r)
+        del mods
+        pq.clear_workspaces()
+        torch.cuda.empty_cache()
+    print("# slowest ratio (tile path / streaming path) by grouped rows: " + ", ".join(f"{m} rows x{r:.2f}" for m, r in sorted(worst.items())))
+    print(f"# clocks after: {sclk()}")
+
+
 def one_forward(dev):
     """for a kernel trace: per plumbing, one warm forward (not listed) and then ONE forward between two marker kernels (torch's bitwise_not on 7 elements)"""
     name, E, k, H, inter, _ = CASES[0]
@@ -197,6 +250,8 @@ def main():
     if "--one-forward" in sys.argv:
         return one_forward(dev)
     quick = "--quick" in sys.argv
+    if "--decode" in sys.argv:
+        return decode(dev, quick)
     print(f"# {torch.cuda.get_device_name(0)}; {time.strftime('%Y-%m-%d')}; medians [min .. max] of hipGraph replays, the two plumbings replayed in turn; bf16")
     print(f"# clocks before: {sclk()}")
     for (name, E, k, H, inter, kinds) in CASES:
