@@ -82,6 +82,18 @@ int32_t pq_silu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, in
                                   int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale,
                                   void* h_out, int64_t ld_h, void* stream);
 
+/* K1 fused into the CLAMPED gates of a gated expert MLP: quantize(h) per token in one pass, h by QSPEC G1-G5, L = limit rounded to `dtype`:
+ *   kind PQ_GLU_CLAMPED_SILU  (DeepSeek-V4's experts):  h = silu(min(g, L)) * clamp(u, -L, +L)
+ *   kind PQ_GLU_ALPHA_SIGMOID (GPT-OSS's experts):      gc = min(g, L);  h = (clamp(u, -L, +L) + 1) * (gc * sigmoid(alpha * gc))
+ * with a storage rounding after every step a chain of tensor ops would round at; a NaN in g or u propagates, then Q1-Q6 on the rows of h.  Layouts and argument
+ * meaning as pq_silu_mul_quant_rowwise (g, u: the two column halves of one [rows, 2 cols] tensor qualify, ld = 2 cols; h_out nullable).  limit must be finite, > 0
+ * and must not round to zero in `dtype`; alpha must be finite (it is not read for PQ_GLU_CLAMPED_SILU).  A bad kind / dtype / limit / alpha is PQ_ERR_BAD_ARG before
+ * any HIP call; rows == 0 or cols == 0 is a no-op. */
+#define PQ_GLU_CLAMPED_SILU 0
+#define PQ_GLU_ALPHA_SIGMOID 1
+int32_t pq_glu_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, float limit,
+                             float alpha, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* The two halves of pq_silu_mul_quant_rowwise for an intermediate whose COLUMNS are sharded over ranks (BASELINE config 5, gate/up and down both
  * column-sharded): a rank holds g, u[rows, cols_local].  The row amax of h = silu(g)*u is an exact max, so
  *   pq_silu_mul_rowamax            -> amax_bits[rows]: the f32 bit pattern of max |h| over the LOCAL columns (non-negative floats and NaNs order as
@@ -298,6 +310,11 @@ int32_t pq_selftest_half_encode(int32_t dtype, unsigned long long* counts, void*
  * one-correction division the producer kernel uses, the two-correction form and true division.  counts[0] += patterns, counts[1] +=
  * patterns whose stored silu(g) differs between the first two, counts[2] += between the last two.  counts[3] zeroed by the caller.  QSPEC S4. */
 int32_t pq_selftest_silu_short(int32_t dtype, unsigned long long* counts, void* stream);
+
+/* Self-test hook: every 16-bit pattern g on which pq_glu_quant_rowwise takes its division-free sequence for this (kind, limit, alpha) through that sequence and
+ * through the specified one (true division), against two values of u.  counts[0] += patterns, counts[1] += patterns whose stored h differs.  counts[2] zeroed by the
+ * caller.  QSPEC G2-G5. */
+int32_t pq_selftest_glu_short(int32_t dtype, int32_t kind, float limit, float alpha, unsigned long long* counts, void* stream);
 
 /* Name of the single-pass GEMM kernel variant the dispatcher would pick for this problem (static string); with a workspace
  * (pq_qlinear_workspace_bytes > 0) pq_qlinear_s8 runs a split-K form of the 256 x 256 (or 128 x 256) tile instead. */

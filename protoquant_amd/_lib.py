@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libpq_hip.so")
 ABI_VERSION = 1
 
 PQ_BF16, PQ_FP16, PQ_F32 = 0, 1, 2
+GLU_KINDS = {"clamped_silu": 0, "alpha_sigmoid": 1}        # PQ_GLU_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
 EXPORTS = (
@@ -25,6 +26,7 @@ EXPORTS = (
     "pq_qlinear_s8_grouped", "pq_gemm_s8s8s32_grouped", "pq_grouped_variant_name",
     "pq_qlinear_s8_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", "pq_grouped_stream_plan_name",
     "pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine",
+    "pq_glu_quant_rowwise", "pq_selftest_glu_short",
 )
 
 _lib = None
@@ -105,6 +107,10 @@ def lib() -> ctypes.CDLL:
     L.pq_moe_combine.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, i64, vp, i64, vp]
     L.pq_silu_mul_quant_rowwise.restype = i32
     L.pq_silu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_glu_quant_rowwise.restype = i32
+    L.pq_glu_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, i32, ctypes.c_float, ctypes.c_float, vp, i64, vp, vp, i64, vp]
+    L.pq_selftest_glu_short.restype = i32
+    L.pq_selftest_glu_short.argtypes = [i32, i32, ctypes.c_float, ctypes.c_float, vp, vp]
     L.pq_rmsnorm_quant_rowwise.restype = i32
     L.pq_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_set_option.restype = i32

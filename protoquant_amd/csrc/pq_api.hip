@@ -39,6 +39,9 @@ void set_stamp_buffer(unsigned long long*);
 void launch_fast_quotient_check(const uint32_t*, const uint32_t*, int64_t, unsigned long long*, hipStream_t);
 void launch_half_encode_check(int, unsigned long long*, hipStream_t);
 void launch_silu_short_check(int, unsigned long long*, hipStream_t);
+template <int DT> void glu_quant_dispatch(int, const void*, int64_t, const void*, int64_t, int64_t, int64_t, float, float, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+float glu_limit_in_dtype(int, float);
+void launch_glu_short_check(int, int, float, float, unsigned long long*, hipStream_t);
 }  // namespace pq
 
 namespace {
@@ -411,6 +414,33 @@ int32_t pq_silu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, in
         default: pq::silu_mul_quant_dispatch<PQ_F32>(g, ld_g, u, ld_u, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
     }
     return check_launch("pq_silu_mul_quant_rowwise");
+}
+
+// kind / dtype / limit / alpha of the clamped gates, shared by the kernel entry and its self-test; nullptr = fine
+static const char* glu_bad_params(int32_t dtype, int32_t kind, float limit, float alpha) {
+    if (dtype < 0 || dtype > 2) return "unknown dtype";
+    if (kind != PQ_GLU_CLAMPED_SILU && kind != PQ_GLU_ALPHA_SIGMOID) return "unknown kind (0 = clamped silu, 1 = alpha sigmoid)";
+    if (!(limit > 0.0f) || limit > 3.4028234e38f) return "limit must be finite and > 0";
+    if (!(pq::glu_limit_in_dtype(dtype, limit) > 0.0f)) return "limit rounds to zero in the storage dtype";
+    if (!(alpha == alpha) || alpha > 3.4028234e38f || alpha < -3.4028234e38f) return "alpha must be finite";
+    return nullptr;
+}
+
+int32_t pq_glu_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, float limit,
+                             float alpha, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:glu_quant (K1g)");
+    if (const char* why = glu_bad_params(dtype, kind, limit, alpha))
+        return fail(PQ_ERR_BAD_ARG, "pq_glu_quant_rowwise: %s (dtype=%d kind=%d limit=%g alpha=%g)", why, dtype, kind, (double)limit, (double)alpha);
+    if (bad_mat(g, rows, cols, ld_g) || bad_mat(u, rows, cols, ld_u) || bad_mat(q, rows, cols, ld_q) || (rows > 0 && !scale) || (h_out && ld_h < cols))
+        return fail(PQ_ERR_BAD_ARG, "pq_glu_quant_rowwise: bad matrix (rows=%lld cols=%lld ld_g=%lld ld_u=%lld ld_q=%lld ld_h=%lld)", (long long)rows, (long long)cols, (long long)ld_g, (long long)ld_u, (long long)ld_q, (long long)ld_h);
+    if (rows == 0 || cols == 0) return PQ_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case PQ_BF16: pq::glu_quant_dispatch<PQ_BF16>(kind, g, ld_g, u, ld_u, rows, cols, limit, alpha, q, ld_q, scale, h_out, ld_h, st); break;
+        case PQ_FP16: pq::glu_quant_dispatch<PQ_FP16>(kind, g, ld_g, u, ld_u, rows, cols, limit, alpha, q, ld_q, scale, h_out, ld_h, st); break;
+        default: pq::glu_quant_dispatch<PQ_F32>(kind, g, ld_g, u, ld_u, rows, cols, limit, alpha, q, ld_q, scale, h_out, ld_h, st); break;
+    }
+    return check_launch("pq_glu_quant_rowwise");
 }
 
 int32_t pq_silu_mul_rowamax(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols,
@@ -1033,6 +1063,13 @@ int32_t pq_selftest_silu_short(int32_t dtype, unsigned long long* counts, void* 
     if (!counts || (dtype != PQ_BF16 && dtype != PQ_FP16)) return fail(PQ_ERR_BAD_ARG, "pq_selftest_silu_short: dtype must be bf16 or fp16, counts non-null");
     pq::launch_silu_short_check(dtype, counts, static_cast<hipStream_t>(stream));
     return check_launch("pq_selftest_silu_short");
+}
+
+int32_t pq_selftest_glu_short(int32_t dtype, int32_t kind, float limit, float alpha, unsigned long long* counts, void* stream) {
+    if (!counts || (dtype != PQ_BF16 && dtype != PQ_FP16)) return fail(PQ_ERR_BAD_ARG, "pq_selftest_glu_short: dtype must be bf16 or fp16, counts non-null");
+    if (const char* why = glu_bad_params(dtype, kind, limit, alpha)) return fail(PQ_ERR_BAD_ARG, "pq_selftest_glu_short: %s", why);
+    pq::launch_glu_short_check(dtype, kind, limit, alpha, counts, static_cast<hipStream_t>(stream));
+    return check_launch("pq_selftest_glu_short");
 }
 
 #ifdef PQ_ABLATION_BUILD

@@ -10,7 +10,8 @@ MoEGatedMLP      forward(hidden[T, H], topk_ids[T, k], topk_weights[T, k]): quan
 swap_moe_experts replaces the routed experts of a decoder's sparse MoE blocks, in either layout model code holds them in: an `experts` module with two stacked
                  parameters gate_up_proj [E, 2 I, H] / down_proj [E, H, I] called as experts(hidden, top_k_index, top_k_weights) (fused_experts_parts: only that module is
                  replaced, by MoEGatedMLP — router, shared experts and the block's return type stay the model's), or a ModuleList `experts` of gated MLPs next to a
-                 Linear router `gate` (moe_block_parts: the block is replaced by MoEBlock)
+                 Linear router `gate` (moe_block_parts: the block is replaced by MoEBlock).  With gates=... also the experts whose gate is not a plain silu —
+                 GPT-OSS's clamped alpha-sigmoid, DeepSeek-V4's clamped silu (clamped_experts_parts; glu_quantize stands where silu_mul_quantize does)
 
 route_plan and combine are the same two steps as pure tensor code that runs on any device: the DEFINITION moe_route and moe_combine are held to, element for element and
 bit for bit (tests/test_gpu_moe_route.py, tests/test_gpu_moe_combine.py), and what MoEGatedMLP runs with torch_plumbing = True (A/B: tools/moe_layer_bench.py).  The expert
@@ -26,7 +27,7 @@ from torch import nn
 
 from . import _lib as L
 from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8_grouped, qlinear_s8_grouped_stream
-from .qtensor import QTensor, quantize, silu_mul_quantize
+from .qtensor import QTensor, glu_params, glu_quantize, quantize, silu_mul_quantize
 
 
 # Grouped rows up to which GroupedQLinear.forward takes the weight-streaming grouped kernel.  From profiles/r11_moe_decode_bench.txt: the largest of 64 / 32 / 16 / 0 at which
@@ -201,19 +202,56 @@ def moe_combine(y: torch.Tensor, rows_of: torch.Tensor, slot_of: torch.Tensor, t
     return out
 
 
+GATE_KINDS = ("silu", "clamped_silu", "alpha_sigmoid")
+
+
+def _gate_kinds(gates) -> tuple:
+    """the `gates` argument of swap_moe_experts / prepare_for_int8 / convert_checkpoint as a tuple of kinds: "all", one kind, or an iterable of kinds"""
+    kinds = GATE_KINDS if gates == "all" else ((gates,) if isinstance(gates, str) else tuple(gates))
+    if any(k not in GATE_KINDS for k in kinds):
+        raise ValueError(f"unknown gate kind in {gates!r}: expected \"all\" or any of {GATE_KINDS}")
+    return kinds
+
+
+def standard_stacked(gate_up_proj: torch.Tensor, down_proj: torch.Tensor, gate_up_bias=None, down_bias=None, transposed: bool = False, interleaved: bool = False):
+    """Stacked expert parameters in the order model code stores them -> (gate_up [E, 2 I, H], down [E, H, I], gate_up_bias [E, 2 I] | None, down_bias [E, H] | None) in the
+    order the library reads: y = x @ W[e].T, per expert the gate rows, then the up rows.  transposed: the parameters are stored [E, in, out] (y = x @ W[e]);
+    interleaved: gate / up alternate along the output axis (even outputs become rows 0 .. I - 1, odd outputs rows I .. 2 I - 1, the bias permuted alike)."""
+    gu, dn = gate_up_proj, down_proj
+    if transposed:
+        gu, dn = gu.transpose(1, 2), dn.transpose(1, 2)
+    if interleaved:
+        gu = torch.cat([gu[:, 0::2], gu[:, 1::2]], dim=1)
+        if gate_up_bias is not None:
+            gate_up_bias = torch.cat([gate_up_bias[:, 0::2], gate_up_bias[:, 1::2]], dim=1)
+    return gu.contiguous(), dn.contiguous(), gate_up_bias, down_bias
+
+
 class MoEGatedMLP(nn.Module):
-    """The E gated expert MLPs of a mixture-of-experts block: out[t] = sum_j w[t, j] * down_e(silu(gate_e(x_t)) * up_e(x_t)), e = topk_ids[t, j].
-    gate_up: GroupedQLinear [E, 2 I, H] (gate rows, then up rows, per expert); down: GroupedQLinear [E, H, I].
+    """The E gated expert MLPs of a mixture-of-experts block: out[t] = sum_j w[t, j] * down_e(act(gate_e(x_t), up_e(x_t))), e = topk_ids[t, j].
+    gate_up: GroupedQLinear [E, 2 I, H] (gate rows, then up rows, per expert); down: GroupedQLinear [E, H, I]; a bias of `down` is added before the routing weight
+    multiplies, (x @ W + b) * w.
+    gate_kind (plain attributes, not part of the state dict): "silu" — act = silu(g) * u (silu_mul_quantize); "clamped_silu" — silu(min(g, L)) * clamp(u, +-L), L =
+    gate_limit (DeepSeek-V4); "alpha_sigmoid" — (clamp(u, +-L) + 1) * gc * sigmoid(gate_alpha * gc), gc = min(g, L) (GPT-OSS); the last two through glu_quantize.
     torch_plumbing = True runs the routing sort and the combine as the stock torch ops of route_plan / combine instead of the library's kernels — same bits (A/B, tests)."""
 
     torch_plumbing = False
 
-    def __init__(self, gate_up: GroupedQLinear, down: GroupedQLinear):
+    def __init__(self, gate_up: GroupedQLinear, down: GroupedQLinear, gate_kind: str = "silu", gate_limit: float | None = None, gate_alpha: float | None = None):
         super().__init__()
         if gate_up.num_experts != down.num_experts or gate_up.out_features != 2 * down.in_features:
             raise ValueError("MoEGatedMLP: gate_up must map to 2 x down.in_features, for the same experts")
+        if gate_kind not in GATE_KINDS:
+            raise ValueError(f"MoEGatedMLP: unknown gate_kind {gate_kind!r}, expected one of {GATE_KINDS}")
+        if gate_kind != "silu":
+            _, gate_limit, gate_alpha = glu_params(gate_kind, gate_limit, gate_alpha)
+            if gate_kind == "clamped_silu":
+                gate_alpha = None
+        elif gate_limit is not None or gate_alpha is not None:
+            raise ValueError("MoEGatedMLP: gate_limit / gate_alpha belong to the clamped gate kinds, not to \"silu\"")
         self.gate_up, self.down = gate_up, down
         self.num_experts = gate_up.num_experts
+        self.gate_kind, self.gate_limit, self.gate_alpha = gate_kind, gate_limit, gate_alpha
 
     @classmethod
     def from_experts(cls, experts) -> "MoEGatedMLP":
@@ -222,14 +260,24 @@ class MoEGatedMLP(nn.Module):
         return cls(GroupedQLinear.from_linears([m.gate_up for m in mlps]), GroupedQLinear.from_linears([m.down for m in mlps]))
 
     @classmethod
-    def from_stacked(cls, gate_up_proj: torch.Tensor, down_proj: torch.Tensor) -> "MoEGatedMLP":
+    def from_stacked(cls, gate_up_proj: torch.Tensor, down_proj: torch.Tensor, gate_up_bias: torch.Tensor | None = None, down_bias: torch.Tensor | None = None,
+                     transposed: bool = False, interleaved: bool = False, gate_kind: str = "silu", gate_limit: float | None = None,
+                     gate_alpha: float | None = None) -> "MoEGatedMLP":
         """The experts as model code holds them since transformers 5: gate_up_proj [E, 2 I, H] (per expert the gate rows, then the up rows; y = x @ W[e].T) and
-        down_proj [E, H, I], float, on the GPU.  Every row is quantised per output channel (GroupedQLinear.from_weight): the codes and scales from_experts gives for
-        the E (gate, up, down) slices taken as nn.Linear layers."""
-        if gate_up_proj.dim() != 3 or down_proj.dim() != 3 or gate_up_proj.shape[0] != down_proj.shape[0] or gate_up_proj.shape[2] != down_proj.shape[1] or \
-                gate_up_proj.shape[1] != 2 * down_proj.shape[2]:
-            raise ValueError(f"MoEGatedMLP.from_stacked: expected gate_up_proj [E, 2 I, H] and down_proj [E, H, I], got {tuple(gate_up_proj.shape)} and {tuple(down_proj.shape)}")
-        return cls(GroupedQLinear.from_weight(gate_up_proj), GroupedQLinear.from_weight(down_proj))
+        down_proj [E, H, I], float, on the GPU — or, with transposed / interleaved, GPT-OSS's storage: gate_up_proj [E, H, 2 I] with gate / up in alternating columns,
+        down_proj [E, I, H], gate_up_bias [E, 2 I] interleaved alike, down_bias [E, H].  The conversion to the standard order (standard_stacked) happens once, here.
+        Every row is quantised per output channel (GroupedQLinear.from_weight): the codes and scales from_experts gives for the E (gate, up, down) slices taken as
+        nn.Linear layers; per-channel quantisation commutes with the row permutation."""
+        if gate_up_proj.dim() != 3 or down_proj.dim() != 3:
+            raise ValueError(f"MoEGatedMLP.from_stacked: expected 3-D stacked parameters, got {tuple(gate_up_proj.shape)} and {tuple(down_proj.shape)}")
+        gu, dn, gub, dnb = standard_stacked(gate_up_proj, down_proj, gate_up_bias, down_bias, transposed, interleaved)
+        if gu.shape[0] != dn.shape[0] or gu.shape[2] != dn.shape[1] or gu.shape[1] != 2 * dn.shape[2]:
+            raise ValueError(f"MoEGatedMLP.from_stacked: expected gate_up_proj [E, 2 I, H] and down_proj [E, H, I]{' (stored transposed)' if transposed else ''}, "
+                             f"got {tuple(gate_up_proj.shape)} and {tuple(down_proj.shape)}")
+        for b, n, what in ((gub, gu.shape[1], "gate_up_bias"), (dnb, dn.shape[1], "down_bias")):
+            if b is not None and tuple(b.shape) != (gu.shape[0], n):
+                raise ValueError(f"MoEGatedMLP.from_stacked: {what} must be [E, {n}], got {tuple(b.shape)}")
+        return cls(GroupedQLinear.from_weight(gu, gub), GroupedQLinear.from_weight(dn, dnb), gate_kind, gate_limit, gate_alpha)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         H = hidden.shape[-1]
@@ -244,11 +292,19 @@ class MoEGatedMLP(nn.Module):
         else:
             row_index, offsets, rows_of, slot_of, xs = moe_route(ids, self.num_experts, xs=xq.scale.reshape(-1))
         gu = self.gate_up(xq, offsets, row_index, xs)                  # [T k, 2 I]: the codes are read where the tokens lie
-        h = silu_mul_quantize(gu[:, :inter], gu[:, inter:])            # sorted rows: int8 codes + row scales
+        if self.gate_kind == "silu":
+            h = silu_mul_quantize(gu[:, :inter], gu[:, inter:])        # sorted rows: int8 codes + row scales
+        else:
+            h = glu_quantize(gu[:, :inter], gu[:, inter:], self.gate_kind, self.gate_limit, self.gate_alpha)
         y = self.down(h, offsets)
         if self.torch_plumbing:
             return combine(y, rows_of, slot_of, w).reshape(hidden.shape)
         return moe_combine(y, rows_of, slot_of, w).reshape(hidden.shape)
+
+    def extra_repr(self):
+        if self.gate_kind == "silu":
+            return "gate_kind=silu"
+        return f"gate_kind={self.gate_kind}, gate_limit={self.gate_limit}" + (f", gate_alpha={self.gate_alpha}" if self.gate_alpha is not None else "")
 
 
 class MoEBlock(nn.Module):
@@ -373,20 +429,110 @@ def fused_experts_parts(mod: nn.Module):
     return FusedExperts(E, H, I, False, False, True)
 
 
-def swap_moe_experts(model: nn.Module) -> int:
+class ClampedExperts(NamedTuple):
+    """What clamped_experts_parts reports of an experts module whose gate is one of the two clamped kinds: the shapes, which biases it has, how the parameters are
+    stored (standard_stacked turns them into the library's order) and the gate (MoEGatedMLP's gate_kind / gate_limit / gate_alpha)."""
+    num_experts: int
+    hidden: int
+    intermediate: int
+    gate_up_bias: bool
+    down_bias: bool
+    transposed: bool          # gate_up_proj is [E, H, 2 I], down_proj [E, I, H]: y = x @ W[e]
+    interleaved: bool         # gate / up alternate along the output axis of gate_up_proj (and of its bias) instead of lying in two halves
+    gate_kind: str            # "clamped_silu" | "alpha_sigmoid"
+    limit: float
+    alpha: float | None
+
+
+def _probe_gate(mod: nn.Module, interleaved: bool, kind: str, limit: float, alpha) -> bool:
+    """Attributes cannot prove what an _apply_gate computes: run the module's own on a small fixed CPU tensor — gate and up values inside and beyond +-limit, both
+    signs, laid out as the module is claimed to read them — and compare with the float64 restatement of the claimed kind."""
+    base = torch.tensor([-3.0, -1.5, -1.0, -0.6, -0.1, 0.0, 0.3, 0.9, 1.0, 1.25, 2.0, 4.0], dtype=torch.float64) * limit
+    g = torch.stack([base, base.flip(0) * 0.7, base * 0.31])
+    u = torch.stack([base.roll(5), base * 0.45, base.flip(0) * 1.1])
+    packed = torch.stack([g, u], dim=-1).reshape(3, -1) if interleaved else torch.cat([g, u], dim=-1)
+    gc, uc = g.clamp(max=limit), u.clamp(min=-limit, max=limit)
+    want = gc * torch.sigmoid(gc) * uc if kind == "clamped_silu" else (uc + 1) * (gc * torch.sigmoid(alpha * gc))
+    try:
+        with torch.no_grad():
+            got = mod._apply_gate(packed)
+    except Exception:
+        return False
+    return isinstance(got, torch.Tensor) and got.shape == want.shape and bool(torch.allclose(got.to(torch.float64), want, rtol=1e-9, atol=1e-12))
+
+
+def clamped_experts_parts(mod: nn.Module):
+    """A fused-parameter experts module (called as mod(hidden[T, H], indices[T, k], weights[T, k]), as fused_experts_parts describes) whose gate is a method
+    `_apply_gate` of its class and computes one of the two clamped gates MoEGatedMLP serves — transformers 5's GptOssExperts ("alpha_sigmoid": parameters stored
+    [E, in, out], gate / up in alternating columns, biases) and DeepseekV4Experts ("clamped_silu": Mixtral's storage) — as ClampedExperts; else None, and None for every
+    module fused_experts_parts accepts.  Recognised by shapes, parameter names, the flags model code sets on its experts classes (is_transposed, is_concatenated,
+    has_bias) and the attributes `limit` / `alpha`, never by import; and since attributes do not say what the gate computes, the module's own _apply_gate is probed
+    (_probe_gate): a class that clamps differently, uses another alpha than it states or adds no 1 to `up` is refused."""
+    if isinstance(mod, (nn.ModuleList, MoEGatedMLP)) or fused_experts_parts(mod) is not None:
+        return None
+    own_gate = getattr(type(mod), "_apply_gate", None)
+    if own_gate is None or getattr(own_gate, "__name__", "") == "_default_apply_gate":
+        return None
+    params, act = dict(mod.named_parameters(recurse=False)), getattr(mod, "act_fn", None)
+    has_bias = getattr(mod, "has_bias", False)
+    names = {"gate_up_proj", "down_proj"} | ({"gate_up_proj_bias", "down_proj_bias"} if has_bias is True else set())
+    if has_bias not in (True, False) or set(params) != names or list(mod.named_buffers(recurse=False)) or any(c is not act for c in mod.children()):
+        return None
+    transposed, concatenated = getattr(mod, "is_transposed", False), getattr(mod, "is_concatenated", True)
+    if transposed not in (True, False) or concatenated not in (True, False) or getattr(mod, "has_gate", True) is not True:
+        return None
+    gu, dn = params["gate_up_proj"], params["down_proj"]
+    if gu.dim() != 3 or dn.dim() != 3 or not gu.is_floating_point() or any(p.dtype != gu.dtype for p in params.values()):
+        return None
+    E = gu.shape[0]
+    H, I = (gu.shape[1], dn.shape[1]) if transposed else (gu.shape[2], dn.shape[2])
+    if E < 1 or tuple(gu.shape) != ((E, H, 2 * I) if transposed else (E, 2 * I, H)) or tuple(dn.shape) != ((E, I, H) if transposed else (E, H, I)):
+        return None
+    if has_bias and (tuple(params["gate_up_proj_bias"].shape) != (E, 2 * I) or tuple(params["down_proj_bias"].shape) != (E, H)):
+        return None
+    if any(isinstance(getattr(mod, n, E), int) and getattr(mod, n, E) != E for n in ("num_experts", "num_local_experts")):
+        return None
+    limit, alpha = getattr(mod, "limit", None), getattr(mod, "alpha", None)
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and -float("inf") < v < float("inf")      # noqa: E731
+    if not number(limit) or limit <= 0 or (alpha is not None and not number(alpha)):
+        return None
+    kind = "alpha_sigmoid" if alpha is not None else "clamped_silu"
+    if (kind == "clamped_silu") != _is_silu(act):              # DeepSeek-V4's silu is its act_fn; GPT-OSS has none (its sigmoid is written in the method)
+        return None
+    try:
+        sig = [p.name.lower() for p in inspect.signature(type(mod).forward).parameters.values() if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)][1:]
+    except (TypeError, ValueError):
+        return None
+    if len(sig) != 3 or not any(t in sig[1] for t in ("ind", "idx", "ids")) or not any(t in sig[2] for t in ("weight", "score", "prob")):
+        return None
+    if not _probe_gate(mod, not concatenated, kind, float(limit), None if alpha is None else float(alpha)):
+        return None
+    return ClampedExperts(E, H, I, has_bias, has_bias, transposed, not concatenated, kind, float(limit), None if alpha is None else float(alpha))
+
+
+def swap_moe_experts(model: nn.Module, gates=("silu",)) -> int:
     """Replace, in place, the routed experts of every sparse MoE block of the model: a fused-parameter experts module (fused_experts_parts) by MoEGatedMLP, a block in the
     ModuleList layout (moe_block_parts) by MoEBlock.  The experts' weights are quantised per output channel, the router stays what it was.  Returns the number of
-    blocks whose experts were replaced (0: a dense model, or a layout that is refused, is left untouched — the very same module objects)."""
+    blocks whose experts were replaced (0: a dense model, or a layout that is refused, is left untouched — the very same module objects).
+    gates: the gate kinds to swap — "silu" (the default: the layouts above), "clamped_silu" (DeepSeek-V4) and "alpha_sigmoid" (GPT-OSS), recognised by
+    clamped_experts_parts and swapped only when named; "all" names all three."""
+    kinds = _gate_kinds(gates)
     n = 0
     for name, child in list(model.named_children()):
-        parts = moe_block_parts(child)
+        parts = moe_block_parts(child) if "silu" in kinds else None
+        clamped = clamped_experts_parts(child) if parts is None and len(kinds) > ("silu" in kinds) else None
         if parts is not None:
             lins, top_k, renorm, returns_logits = parts
             setattr(model, name, MoEBlock(child.gate, MoEGatedMLP.from_experts(lins), top_k, renorm, returns_logits))
             n += 1
-        elif fused_experts_parts(child) is not None:
+        elif "silu" in kinds and fused_experts_parts(child) is not None:
             setattr(model, name, MoEGatedMLP.from_stacked(child.gate_up_proj.detach(), child.down_proj.detach()))
             n += 1
+        elif clamped is not None and clamped.gate_kind in kinds:
+            bias = (child.gate_up_proj_bias.detach(), child.down_proj_bias.detach()) if clamped.gate_up_bias else (None, None)
+            setattr(model, name, MoEGatedMLP.from_stacked(child.gate_up_proj.detach(), child.down_proj.detach(), *bias, transposed=clamped.transposed,
+                                                          interleaved=clamped.interleaved, gate_kind=clamped.gate_kind, gate_limit=clamped.limit, gate_alpha=clamped.alpha))
+            n += 1
         else:
-            n += swap_moe_experts(child)
+            n += swap_moe_experts(child, kinds)
     return n

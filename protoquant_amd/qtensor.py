@@ -104,6 +104,45 @@ def silu_mul_quantize(g: torch.Tensor, u: torch.Tensor, return_h: bool = False):
     return (qt, h.reshape(g.shape)) if return_h else qt
 
 
+def glu_params(kind: str, limit, alpha=None):
+    """(kind code, limit, alpha) of a clamped gate as pq_glu_quant_rowwise takes them, checked: kind "clamped_silu" (DeepSeek-V4: silu(min(g, L)) * clamp(u, +-L)) or
+    "alpha_sigmoid" (GPT-OSS: (clamp(u, +-L) + 1) * gc * sigmoid(alpha * gc), gc = min(g, L)), limit finite and > 0, alpha finite (required for alpha_sigmoid only)."""
+    if kind not in L.GLU_KINDS:
+        raise ValueError(f"glu_quantize: unknown kind {kind!r}, expected one of {sorted(L.GLU_KINDS)}")
+    if limit is None or not 0.0 < float(limit) < float("inf"):
+        raise ValueError(f"glu_quantize: limit must be finite and > 0, got {limit!r}")
+    if alpha is None:
+        if kind == "alpha_sigmoid":
+            raise ValueError("glu_quantize: kind 'alpha_sigmoid' needs alpha")
+        alpha = 0.0
+    if not -float("inf") < float(alpha) < float("inf"):
+        raise ValueError(f"glu_quantize: alpha must be finite, got {alpha!r}")
+    return L.GLU_KINDS[kind], float(limit), float(alpha)
+
+
+def glu_quantize(g: torch.Tensor, u: torch.Tensor, kind: str, limit: float, alpha: float | None = None, return_h: bool = False):
+    """quantize(h, axis=-1) in ONE pass for the clamped gates of GPT-OSS's and DeepSeek-V4's experts (glu_params names them), the way silu_mul_quantize fuses
+    F.silu(g) * u: h is computed, reduced and encoded in registers.  g and u may be the column halves of one fused gate+up output.  Numerics: QSPEC G1-G6 — for
+    bf16 / fp16 rows h holds the values transformers' _apply_gate stores, rounding for rounding; the limit is rounded to the rows' dtype as torch.clamp rounds it.
+    return_h=True also returns h in the input dtype (stored by the same kernel)."""
+    L.require_gpu(g, "glu_quantize(g)")
+    L.require_gpu(u, "glu_quantize(u)")
+    if g.shape != u.shape or g.dtype != u.dtype or g.device != u.device or g.dim() < 1:
+        raise ValueError(f"glu_quantize: g {tuple(g.shape)} {g.dtype} and u {tuple(u.shape)} {u.dtype} must match")
+    kcode, limit, alpha = glu_params(kind, limit, alpha)
+    code = L.dtype_code(g.dtype)
+    g2, u2 = _rows_view(g), _rows_view(u)
+    rows, cols = g2.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=g.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=g.device)
+    h = torch.empty((rows, cols), dtype=g.dtype, device=g.device) if return_h else None
+    with torch.cuda.device(g.device):
+        L.check(L.lib().pq_glu_quant_rowwise(g2.data_ptr(), L.ld(g2), u2.data_ptr(), L.ld(u2), code, rows, cols, kcode, limit, alpha, q.data_ptr(), max(cols, 1),
+                                             scale.data_ptr(), h.data_ptr() if return_h else None, max(cols, 1), L.stream_ptr(g)), "glu_quantize")
+    qt = QTensor(q.reshape(g.shape), scale, 1, g.dtype, g.shape)
+    return (qt, h.reshape(g.shape)) if return_h else qt
+
+
 def _silu_pair(g, u, what):
     L.require_gpu(g, f"{what}(g)")
     L.require_gpu(u, f"{what}(u)")

@@ -14,7 +14,11 @@ gated MLP                  ``<mlp>.gate_up.{wq,ws}`` (gate then up) and ``<mlp>.
 MoE experts                ``<block>.experts.gate_up.{wq,ws}`` int8 ``[E, 2I, H]`` / fp32 ``[E, 2I]`` and ``<block>.experts.down.{wq,ws}``
                            ``[E, H, I]`` / ``[E, H]`` — the buffers of a block swapped by ``swap_moe_experts`` (its ``state_dict()``).
                            ``convert_checkpoint(model=...)`` writes them from a checkpoint's stacked ``<block>.experts.gate_up_proj``
-                           ``[E, 2I, H]`` / ``<block>.experts.down_proj`` ``[E, H, I]`` for the experts modules ``fused_experts_parts`` recognises
+                           ``[E, 2I, H]`` / ``<block>.experts.down_proj`` ``[E, H, I]`` for the experts modules ``fused_experts_parts`` recognises.
+                           With ``moe_gates=...`` also for the clamped gates ``clamped_experts_parts`` recognises (GPT-OSS, DeepSeek-V4): always in the
+                           standard order above — GPT-OSS's ``gate_up_proj`` ``[E, H, 2I]`` (gate / up in alternating columns) is transposed and its
+                           rows permuted once, here, ``gate_up_proj_bias`` / ``down_proj_bias`` become ``<block>.experts.gate_up.bias`` ``[E, 2I]`` (permuted
+                           alike) / ``<block>.experts.down.bias`` ``[E, H]``
 column shard (rank r of G) rows ``shard_bounds(N, G, r)`` of ``wq`` / ``ws`` / ``bias`` under ``<mod>.local.*``
 row shard (rank r of G)    columns ``shard_bounds(K, G, r)`` of ``wq``, the FULL-row ``ws``, the bias on rank 0 only, under
                            ``<mod>.local.*``
@@ -33,7 +37,7 @@ import torch
 from torch import nn
 
 from .qlinear import FusedQLinear, GatedMLP, _is_silu, is_plain_linear, qlinear
-from .moe import GroupedQLinear, MoEBlock, MoEGatedMLP, fused_experts_parts, moe_block_parts
+from .moe import GroupedQLinear, MoEBlock, MoEGatedMLP, _gate_kinds, clamped_experts_parts, fused_experts_parts, moe_block_parts, standard_stacked
 from .qtensor import quantize
 from .sharded import ColumnShardedQLinear, RowShardedQLinear, ShardedGatedMLP, shard_bounds
 
@@ -54,7 +58,7 @@ def _quant_rows(w: torch.Tensor, device):
 def convert_checkpoint(state_dict: dict, *, device="cuda", is_linear: Callable[[str, torch.Tensor], bool] = default_is_linear,
                        fuse: dict[str, Iterable[str]] | None = None, gated_mlp: Iterable[str] = (),
                        column_sharded: Iterable[str] = (), row_sharded: Iterable[str] = (), sharded_gated_mlp: Iterable[str] = (),
-                       world: int = 1, rank: int = 0, out_device="cpu", model: nn.Module | None = None) -> dict:
+                       world: int = 1, rank: int = 0, out_device="cpu", model: nn.Module | None = None, moe_gates=("silu",)) -> dict:
     """state_dict of float weights -> state_dict in FORMAT.
 
     model: the FLOAT model the checkpoint belongs to (a meta-device instance is enough).  When given, exactly the weights of its
@@ -64,6 +68,7 @@ def convert_checkpoint(state_dict: dict, *, device="cuda", is_linear: Callable[[
       `weight` would be quantised at all), and the stacked 3-D parameters of its fused MoE experts modules (fused_experts_parts)
       are quantised per expert and output channel into ``<experts>.gate_up.*`` / ``<experts>.down.*``.  Without `model` a 3-D
       parameter is copied through as it is: a state_dict does not say how an experts module lays out or uses it.
+    moe_gates: the gate kinds whose experts are converted, as swap_moe_experts(model, gates=...) takes them: "silu" (default), "clamped_silu", "alpha_sigmoid", "all".
 
     fuse: ``{"layers.0.attn.qkv": ["layers.0.attn.q_proj", "layers.0.attn.k_proj", "layers.0.attn.v_proj"]}`` — the members
       are replaced by one FusedQLinear entry.  gated_mlp: prefixes of modules with gate_proj / up_proj / down_proj children
@@ -92,25 +97,39 @@ def convert_checkpoint(state_dict: dict, *, device="cuda", is_linear: Callable[[
 
     fused_experts = []
     if model is not None:
+        kinds = _gate_kinds(moe_gates)
         linear_names = {n for n, m in model.named_modules() if is_plain_linear(m)}
         is_linear = lambda name, w: name in linear_names      # noqa: E731
-        fused_experts = [(n, fused_experts_parts(m)) for n, m in model.named_modules() if fused_experts_parts(m) is not None]
+        for n, m in model.named_modules():                     # (experts module, its shapes, transposed, interleaved, with biases)
+            parts = fused_experts_parts(m) if "silu" in kinds else None
+            if parts is not None:
+                fused_experts.append((n, parts, False, False, False))
+                continue
+            parts = clamped_experts_parts(m) if len(kinds) > ("silu" in kinds) else None
+            if parts is not None and parts.gate_kind in kinds:
+                fused_experts.append((n, parts, parts.transposed, parts.interleaved, parts.gate_up_bias))
     sd = dict(state_dict)
     out = {}
-    for ep, parts in fused_experts:                    # every experts tensor is looked at before anything is quantised
+    for ep, parts, transposed, _, biased in fused_experts:                    # every experts tensor is looked at before anything is quantised
         E, H, I = parts.num_experts, parts.hidden, parts.intermediate
-        for src, (N, K) in (("gate_up_proj", (2 * I, H)), ("down_proj", (H, I))):
+        want = {"gate_up_proj": (E, H, 2 * I) if transposed else (E, 2 * I, H), "down_proj": (E, I, H) if transposed else (E, H, I)}
+        if biased:
+            want.update(gate_up_proj_bias=(E, 2 * I), down_proj_bias=(E, H))
+        for src, shape in want.items():
             w = sd.get(f"{ep}.{src}")
             if w is None:
                 raise KeyError(f"{ep}.{src}: the model holds fused MoE experts there, the checkpoint has no such tensor")
-            if tuple(w.shape) != (E, N, K):
-                raise ValueError(f"{ep}.{src}: the checkpoint's tensor is {tuple(w.shape)}, the model's experts are [{E}, {N}, {K}]")
-    for ep, _ in fused_experts:
-        for src, dst in (("gate_up_proj", "gate_up"), ("down_proj", "down")):
-            w = sd.pop(f"{ep}.{src}")
+            if tuple(w.shape) != shape:
+                raise ValueError(f"{ep}.{src}: the checkpoint's tensor is {tuple(w.shape)}, the model's experts are {list(shape)}")
+    for ep, _, transposed, interleaved, biased in fused_experts:
+        gub, dnb = (sd.pop(f"{ep}.gate_up_proj_bias").to(device), sd.pop(f"{ep}.down_proj_bias").to(device)) if biased else (None, None)
+        gu, dn, gub, dnb = standard_stacked(sd.pop(f"{ep}.gate_up_proj").to(device), sd.pop(f"{ep}.down_proj").to(device), gub, dnb, transposed, interleaved)
+        for dst, w, b in (("gate_up", gu, gub), ("down", dn, dnb)):
             E, N, K = w.shape
             wq, ws = _quant_rows(w.reshape(E * N, K), device)
             out[f"{ep}.{dst}.wq"], out[f"{ep}.{dst}.ws"] = wq.reshape(E, N, K).to(out_device), ws.reshape(E, N).to(out_device)
+            if b is not None:
+                out[f"{ep}.{dst}.bias"] = b.contiguous().to(out_device)
     lin = {k[:-len(".weight")]: v for k, v in sd.items() if k.endswith(".weight") and is_linear(k[:-len(".weight")], v)}
     used = set()
 
@@ -208,11 +227,12 @@ def empty_grouped_qlinear(num_experts: int, in_features: int, out_features: int,
 
 
 def empty_moe_gated_mlp(num_experts: int, hidden: int, intermediate: int, bias: bool = False, down_bias: bool | None = None, dtype=torch.bfloat16,
-                        device=None) -> MoEGatedMLP:
+                        device=None, gate_kind: str = "silu", gate_limit: float | None = None, gate_alpha: float | None = None) -> MoEGatedMLP:
     """The receiving module of a swapped MoE block's experts: ``<block>.experts.gate_up.{wq,ws}`` [E, 2 I, H] / [E, 2 I] (gate rows then up rows, per expert) and
     ``<block>.experts.down.{wq,ws}`` [E, H, I] / [E, H] — what ``swap_moe_experts(model).state_dict()`` holds."""
     return MoEGatedMLP(empty_grouped_qlinear(num_experts, hidden, 2 * intermediate, bias, dtype, device),
-                       empty_grouped_qlinear(num_experts, intermediate, hidden, bias if down_bias is None else down_bias, dtype, device))
+                       empty_grouped_qlinear(num_experts, intermediate, hidden, bias if down_bias is None else down_bias, dtype, device),
+                       gate_kind, gate_limit, gate_alpha)
 
 
 def empty_column_sharded(in_features: int, out_features: int, bias: bool, world: int, rank: int, dtype=torch.bfloat16, device=None,
@@ -235,20 +255,30 @@ def empty_sharded_gated_mlp(hidden: int, intermediate: int, world: int, rank: in
     return ShardedGatedMLP(gate_up, down)
 
 
-def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False) -> nn.Module:
+def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False, moe_gates=("silu",)) -> nn.Module:
     """The structural half of swap_linears() and swap_moe_experts(): replace every nn.Linear (and, with fuse_gated_mlp, every Llama-style MLP; and the routed experts
     of every sparse MoE block swap_moe_experts would swap, in either layout) by an EMPTY int8 module of the same shape — no quantisation, no float weights needed (works on meta-device models) — so that
     ``model.load_state_dict(convert_checkpoint(...))`` fills it.  Empty buffers live on the linear's device unless it is meta,
-    then on the CPU; move the model to the GPU after loading."""
+    then on the CPU; move the model to the GPU after loading.
+    moe_gates: the gate kinds whose experts are replaced, as swap_moe_experts(model, gates=...) takes them; for the clamped kinds the receiving MoEGatedMLP gets its
+    gate kind, limit and alpha from the model's own experts module (clamped_experts_parts)."""
+    kinds = _gate_kinds(moe_gates)
     for name, child in list(model.named_children()):
-        fused = fused_experts_parts(child) if (predicate is None or predicate(name, child)) else None
+        wanted = predicate is None or predicate(name, child)
+        fused = fused_experts_parts(child) if wanted and "silu" in kinds else None
+        clamped = clamped_experts_parts(child) if wanted and fused is None and len(kinds) > ("silu" in kinds) else None
+        if clamped is not None and clamped.gate_kind in kinds:
+            p = child.gate_up_proj
+            setattr(model, name, empty_moe_gated_mlp(clamped.num_experts, clamped.hidden, clamped.intermediate, clamped.gate_up_bias, clamped.down_bias, p.dtype,
+                                                     None if p.device.type == "meta" else p.device, clamped.gate_kind, clamped.limit, clamped.alpha))
+            continue
         if fused is not None:
             # fused-parameter experts (transformers 5): only that module is replaced, as swap_moe_experts does — EMPTY stacked experts of the same shape
             p = child.gate_up_proj
             setattr(model, name, empty_moe_gated_mlp(fused.num_experts, fused.hidden, fused.intermediate, fused.gate_up_bias, fused.down_bias, p.dtype,
                                                      None if p.device.type == "meta" else p.device))
             continue
-        moe = moe_block_parts(child) if (predicate is None or predicate(name, child)) else None
+        moe = moe_block_parts(child) if wanted and "silu" in kinds else None
         if moe is not None:
             # a block swap_moe_experts would swap: the same wrapper around EMPTY stacked experts (the router stays a float nn.Linear, as swap_moe_experts leaves it),
             # so the state_dict of a swapped model loads without the float expert weights
@@ -271,7 +301,7 @@ def prepare_for_int8(model: nn.Module, predicate=None, fuse_gated_mlp: bool = Fa
             dev = None if child.weight.device.type == "meta" else child.weight.device
             setattr(model, name, empty_qlinear(child.in_features, child.out_features, child.bias is not None, child.weight.dtype, dev))
         else:
-            prepare_for_int8(child, predicate, fuse_gated_mlp)
+            prepare_for_int8(child, predicate, fuse_gated_mlp, kinds)
     return model
 
 
