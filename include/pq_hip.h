@@ -125,6 +125,18 @@ int32_t pq_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight
                                  int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale,
                                  void* h_out, int64_t ld_h, void* stream);
 
+/* K1a — the residual add fused into pq_rmsnorm_quant_rowwise: s = cast_rne(f32(x) + f32(residual)) is STORED to sum_out (the new residual stream) and its rows
+ * AS STORED go through N1-N6 and Q1-Q6 from the registers that hold them.  QSPEC A1: one binary32 add and one storage rounding per element,
+ * which is what an eager add of two bf16 / fp16 / f32 tensors computes, so q, scale, sum_out and h_out are those of pq_rmsnorm_quant_rowwise run on residual + x,
+ * bit for bit (a NaN propagates; NaNs compare as a class).  Reads 2 x elem bytes, writes elem bytes + 1 B/elem + 4 B/row: 7 B/elem for 16-bit rows against 9 for
+ * the add and K1n as two launches.
+ * sum_out is required and may BE x or residual (the same pointer AND the same leading dimension): every element is read before it is written.  Any other overlap
+ * of sum_out with an input, and any overlap of q, scale or h_out with another operand, returns PQ_ERR_BAD_ARG — as do a null operand, ld < cols, cols >= 2^24, a
+ * negative or non-finite eps and an unknown dtype — before any HIP call, with pq_last_error naming the argument.  h_out may be null.  rows == 0 or cols == 0:
+ * nothing is read or written, returns PQ_OK.  Row layouts and the PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time only, never bits). */
+int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
+                                     int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* dequantize(): out[r,c] = cast_rne(f32(q[r,c]) * scale[axis==0 ? c : r]).  `axis` is the axis the
  * scale was reduced over (1: one scale per row, 0: one scale per column).   QSPEC D1. */
 int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t axis,

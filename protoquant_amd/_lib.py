@@ -27,6 +27,7 @@ EXPORTS = (
     "pq_qlinear_s8_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", "pq_grouped_stream_plan_name",
     "pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine",
     "pq_glu_quant_rowwise", "pq_selftest_glu_short",
+    "pq_add_rmsnorm_quant_rowwise",
 )
 
 _lib = None
@@ -113,6 +114,8 @@ def lib() -> ctypes.CDLL:
     L.pq_selftest_glu_short.argtypes = [i32, i32, ctypes.c_float, ctypes.c_float, vp, vp]
     L.pq_rmsnorm_quant_rowwise.restype = i32
     L.pq_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_add_rmsnorm_quant_rowwise.restype = i32
+    L.pq_add_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_set_option.restype = i32
     L.pq_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     L.pq_selftest_fast_quotient.restype = i32

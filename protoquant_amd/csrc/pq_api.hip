@@ -15,6 +15,7 @@ template <int DT> void quant_rowwise_dispatch(const void*, int64_t, int64_t, int
 template <int DT> hipError_t quant_colwise_dispatch(const void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, hipStream_t);
 template <int DT> void silu_mul_quant_dispatch(const void*, int64_t, const void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 template <int DT> void rmsnorm_quant_dispatch(const void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+template <int DT> void add_rmsnorm_quant_dispatch(const void*, int64_t, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 template <int ODT> void dequant_dispatch(const int8_t*, int64_t, const float*, int, int64_t, int64_t, void*, int64_t, hipStream_t);
 template <int OUT> void launch_gemm_generic(const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t);
 template <int OUT, int TM, int TN> void launch_gemm_fast(const int8_t*, int64_t, const int8_t*, int64_t, const EpiArgs&, int64_t, int64_t, int64_t, hipStream_t);
@@ -528,6 +529,73 @@ int32_t pq_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight
         default: pq::rmsnorm_quant_dispatch<PQ_F32>(x, ld_x, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
     }
     return check_launch("pq_rmsnorm_quant_rowwise");
+}
+
+// Byte extent of a row-major operand of pq_add_rmsnorm_quant_rowwise, and the overlap test between two of them.  Operands that share a leading dimension (column
+// blocks of one buffer) are told apart by the columns they occupy; everything else by its bounding range.
+namespace {
+struct Extent {
+    uintptr_t base;
+    int64_t ld_bytes, width_bytes, rows;
+    uintptr_t end() const { return base + (uintptr_t)((rows - 1) * ld_bytes + width_bytes); }
+};
+Extent extent_of(const void* p, int64_t ld, int64_t rows, int64_t cols, int64_t elem_bytes) {
+    return Extent{reinterpret_cast<uintptr_t>(p), ld * elem_bytes, cols * elem_bytes, rows};
+}
+bool extents_overlap(const Extent& a, const Extent& b) {
+    if (!a.base || !b.base || a.end() <= b.base || b.end() <= a.base) return false;
+    if (a.ld_bytes == b.ld_bytes && a.ld_bytes > 0) {      // the same pitch: disjoint when their column intervals, taken modulo the pitch, do not meet
+        const int64_t ld = a.ld_bytes;
+        const int64_t d = (int64_t)((b.base >= a.base ? b.base - a.base : (uintptr_t)ld - (a.base - b.base) % (uintptr_t)ld) % (uintptr_t)ld);
+        if (d >= a.width_bytes && d + b.width_bytes <= ld) return false;
+    }
+    return true;
+}
+}  // namespace
+
+int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
+                                     int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:add_rmsnorm_quant (K1a)");
+    const char* fn = "pq_add_rmsnorm_quant_rowwise";
+    if (dtype < 0 || dtype > 2) return fail(PQ_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (rows < 0 || cols < 0 || cols >= (1 << 24)) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld; cols < 2^24)", fn, (long long)rows, (long long)cols);
+    if (!(eps >= 0.0f) || eps > 3.4028234e38f) return fail(PQ_ERR_BAD_ARG, "%s: eps must be finite and >= 0 (eps=%g)", fn, (double)eps);
+    if (ld_x < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_x %lld < cols %lld", fn, (long long)ld_x, (long long)cols);
+    if (ld_r < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_r %lld < cols %lld", fn, (long long)ld_r, (long long)cols);
+    if (ld_s < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_s %lld < cols %lld", fn, (long long)ld_s, (long long)cols);
+    if (ld_q < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_q %lld < cols %lld", fn, (long long)ld_q, (long long)cols);
+    if (h_out && ld_h < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_h %lld < cols %lld", fn, (long long)ld_h, (long long)cols);
+    if (rows == 0 || cols == 0) return PQ_OK;
+    if (!x) return fail(PQ_ERR_BAD_ARG, "%s: x is null", fn);
+    if (!residual) return fail(PQ_ERR_BAD_ARG, "%s: residual is null", fn);
+    if (!sum_out) return fail(PQ_ERR_BAD_ARG, "%s: sum_out is null (the sum is the new residual stream: it is always stored)", fn);
+    if (!weight) return fail(PQ_ERR_BAD_ARG, "%s: weight is null", fn);
+    if (!q) return fail(PQ_ERR_BAD_ARG, "%s: q is null", fn);
+    if (!scale) return fail(PQ_ERR_BAD_ARG, "%s: scale is null", fn);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const Extent ex = extent_of(x, ld_x, rows, cols, eb), er = extent_of(residual, ld_r, rows, cols, eb), es = extent_of(sum_out, ld_s, rows, cols, eb),
+                 ew = extent_of(weight, cols, 1, cols, eb), eq = extent_of(q, ld_q, rows, cols, 1), esc = extent_of(scale, rows, 1, rows, 4),
+                 eh = extent_of(h_out, ld_h, rows, cols, eb);
+    // sum_out may BE x or the residual (same base and pitch: every element is read before it is written, by the thread that writes it); any other overlap is refused
+    if (!(sum_out == x && ld_s == ld_x) && extents_overlap(es, ex)) return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps x without being x (same pointer and leading dimension)", fn);
+    if (!(sum_out == residual && ld_s == ld_r) && extents_overlap(es, er))
+        return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps residual without being residual (same pointer and leading dimension)", fn);
+    if (extents_overlap(es, ew)) return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps weight", fn);
+    struct Named { const char* name; const Extent* e; };
+    const Named ins[] = {{"x", &ex}, {"residual", &er}, {"weight", &ew}, {"sum_out", &es}}, outs[] = {{"q", &eq}, {"scale", &esc}, {"h_out", &eh}};
+    for (int o = 0; o < 3; ++o) {
+        for (const Named& i : ins)
+            if (extents_overlap(*outs[o].e, *i.e)) return fail(PQ_ERR_BAD_ARG, "%s: %s overlaps %s", fn, outs[o].name, i.name);
+        for (int o2 = o + 1; o2 < 3; ++o2)
+            if (extents_overlap(*outs[o].e, *outs[o2].e)) return fail(PQ_ERR_BAD_ARG, "%s: %s overlaps %s", fn, outs[o].name, outs[o2].name);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case PQ_BF16: pq::add_rmsnorm_quant_dispatch<PQ_BF16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        case PQ_FP16: pq::add_rmsnorm_quant_dispatch<PQ_FP16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        default: pq::add_rmsnorm_quant_dispatch<PQ_F32>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+    }
+    return check_launch(fn);
 }
 
 int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t axis, int64_t rows, int64_t cols,

@@ -280,4 +280,46 @@ __device__ __forceinline__ void reduce_and_encode(const v4u (&hv)[VPT], uint32_t
     encode_with_amax<DT, VPT, TPR>(hv, row_amax_f32_bits<DT, TPR>(ab), t, nvec, active, row, q, ldq, scale);
 }
 
+// ------------------------------------------------------------------------------------------------
+// QSPEC N1-N5, shared by K1n (producer_kernels.hip) and K1a (addnorm_kernels.hip): ONE copy of the pinned summation order.  The reduction order N1-N3 is the
+// 256-thread layout: vector v on lane v mod 256, xor butterfly per 64 lanes, the four wave sums left to right.
+__device__ __forceinline__ float rms_block_sum(float acc) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+    __shared__ float wsum[4];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+__device__ __forceinline__ float rms_rs(float ss, int cols, float eps) {
+    const float var = ss / (float)cols;
+    return 1.0f / __builtin_sqrtf(var + eps);
+}
+template <int DT>
+__device__ __forceinline__ float rms_h(float x, float w, float rs) {
+    const float xn = Elem<DT>::to_f32(Elem<DT>::from_f32(x * rs));
+    return w * xn;       // the caller rounds to the storage dtype
+}
+
+// one 16-byte vector of x and of the weight -> one 16-byte vector of h (QSPEC N5), two elements per instruction
+template <int DT>
+__device__ __forceinline__ v4u rms_h_vec(const v4u& xv, const v4u& wv, float rs) {
+    v4u out;
+    if constexpr (DT == PQ_F32) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t xb = xv[j], wb = wv[j];      // copies first (hipcc quirk with vector-element lvalues)
+            out[j] = __builtin_bit_cast(uint32_t, rms_h<DT>(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, wb), rs));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t xw = xv[j], ww = wv[j];
+            const v2f xn = Pair<DT>::unpack(Pair<DT>::pack(Pair<DT>::unpack(xw) * splat(rs)));
+            out[j] = Pair<DT>::pack(Pair<DT>::unpack(ww) * xn);
+        }
+    }
+    return out;
+}
+
 }  // namespace pq

@@ -118,45 +118,7 @@ __global__ __launch_bounds__(256) void silu_mul_quant_generic(const void* __rest
 // K1n: RMSNorm fused into the per-token quantisation (QSPEC N1-N6).  One row per 256-thread block (the reduction order N1-N3
 // IS this layout: vector v on lane v mod 256, xor butterfly per 64 lanes, the four wave sums left to right).  Reads x once
 // (2 B/elem) and the weight vector from L2, writes 1 B/elem + 4 B/row: the normalised bf16 activation never goes to HBM.
-__device__ __forceinline__ float rms_block_sum(float acc) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    __shared__ float wsum[4];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-__device__ __forceinline__ float rms_rs(float ss, int cols, float eps) {
-    const float var = ss / (float)cols;
-    return 1.0f / __builtin_sqrtf(var + eps);
-}
-template <int DT>
-__device__ __forceinline__ float rms_h(float x, float w, float rs) {
-    const float xn = Elem<DT>::to_f32(Elem<DT>::from_f32(x * rs));
-    return w * xn;       // the caller rounds to the storage dtype
-}
-
-// one 16-byte vector of x and of the weight -> one 16-byte vector of h (QSPEC N5), two elements per instruction
-template <int DT>
-__device__ __forceinline__ v4u rms_h_vec(const v4u& xv, const v4u& wv, float rs) {
-    v4u out;
-    if constexpr (DT == PQ_F32) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t xb = xv[j], wb = wv[j];      // copies first (hipcc quirk with vector-element lvalues)
-            out[j] = __builtin_bit_cast(uint32_t, rms_h<DT>(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, wb), rs));
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t xw = xv[j], ww = wv[j];
-            const v2f xn = Pair<DT>::unpack(Pair<DT>::pack(Pair<DT>::unpack(xw) * splat(rs)));
-            out[j] = Pair<DT>::pack(Pair<DT>::unpack(ww) * xn);
-        }
-    }
-    return out;
-}
-
+// (rms_block_sum, rms_rs, rms_h, rms_h_vec: producer_device.h — shared with K1a, addnorm_kernels.hip)
 template <int DT, int VPT, bool WRITE_H>
 __global__ __launch_bounds__(256) void rmsnorm_quant_vec(const uint8_t* __restrict__ x, int64_t ldx_bytes, const uint8_t* __restrict__ wgt,
                                                          float eps, int cols, int nvec, int8_t* __restrict__ q, int64_t ldq,

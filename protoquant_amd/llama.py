@@ -9,14 +9,19 @@ q_proj / k_proj / v_proj / o_proj -> post_attention_layernorm -> mlp), SURVEY.md
 The stock attention code keeps calling ``self.q_proj(h)``, ``self.k_proj(h)``, ``self.v_proj(h)``: ``h`` is now a per-token
 ``QTensor`` (it only needs ``.shape`` besides being handed to the projections), the first call runs the fused GEMM and the other
 two return their column slices of its output.  Attention itself (rope, SDPA), the residual adds, the final norm and the embedding
-stay stock torch-ROCm ops.  ``swap_linears(model, fuse_gated_mlp=True)`` must have run first."""
+stay stock torch-ROCm ops.  ``swap_linears(model, fuse_gated_mlp=True)`` must have run first.
+
+``fuse_llama_layers(model, fuse_residual=True)`` (opt-in) also takes the two residual adds of a layer into the norm that follows them
+(``add_rmsnorm_quantize``, kernel K1a: the residual stream is stored once and normalised from registers): see ``ResidualFusedLayer``."""
 from __future__ import annotations
+
+import inspect
 
 import torch
 from torch import nn
 
 from .qlinear import FusedQLinear, GatedMLP, qlinear
-from .qtensor import QTensor, rmsnorm_quantize
+from .qtensor import QTensor, add_rmsnorm_quantize, rmsnorm_quantize
 
 
 class RMSNormQuant(nn.Module):
@@ -27,8 +32,12 @@ class RMSNormQuant(nn.Module):
         self.weight = nn.Parameter(weight.detach().clone(), requires_grad=False)
         self.variance_epsilon = float(eps)
 
-    def forward(self, x: torch.Tensor) -> QTensor:
-        return rmsnorm_quantize(x, self.weight, self.variance_epsilon)
+    def forward(self, x: torch.Tensor, residual: torch.Tensor | None = None):
+        """Without `residual`: the QTensor of RMSNorm(x).  With it: (QTensor of RMSNorm(residual + x), residual + x) from one kernel (K1a) — the bits of the
+        torch add followed by the call without `residual`."""
+        if residual is None:
+            return rmsnorm_quantize(x, self.weight, self.variance_epsilon)
+        return add_rmsnorm_quantize(x, residual, self.weight, self.variance_epsilon)
 
     def extra_repr(self):
         return f"{tuple(self.weight.shape)}, eps={self.variance_epsilon} -> int8 per-token QTensor"
@@ -90,8 +99,223 @@ def _is_rmsnorm(m) -> bool:
     return hasattr(m, "weight") and hasattr(m, "variance_epsilon") and isinstance(getattr(m, "weight"), torch.Tensor) and m.weight.dim() == 1
 
 
-def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool = True) -> int:
-    """Apply the fusions above to every decoder layer found in `model` (in place); returns the number of layers changed."""
+# ---------------------------------------------------------------- the residual adds fused into the norms that follow them (opt-in)
+_CHILDREN = ("input_layernorm", "self_attn", "post_attention_layernorm", "mlp")
+
+
+class _ProbeRefused(Exception):
+    pass
+
+
+class _ProbeLayer:
+    """Stand-in for `self` in a decoder layer class's own forward: the four children are recording functions, every other attribute is read from the real layer —
+    except another module (a dropout, a third norm): a forward that touches one is not the Llama data flow."""
+
+    def __init__(self, layer: nn.Module, children: dict):
+        self.__dict__["_layer"] = layer
+        self.__dict__.update(children)
+
+    def __getattr__(self, name):
+        v = getattr(self.__dict__["_layer"], name)
+        if isinstance(v, nn.Module):
+            raise _ProbeRefused(f"forward reads the submodule {name!r}")
+        return v
+
+
+def _forward_extra_params(cls) -> tuple:
+    """(names of the positional parameters of cls.forward after hidden_states, whether it takes **kwargs)"""
+    ps = list(inspect.signature(cls.forward).parameters.values())[2:]          # (self, hidden_states, ...)
+    names = tuple(p.name for p in ps if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD))
+    return names, any(p.kind == p.VAR_KEYWORD for p in ps)
+
+
+def residual_flow_is_llama(layer: nn.Module, cls=None) -> bool:
+    """True iff `cls.forward` (default: the layer's own class) IS the Llama data flow on this layer:
+
+        r1 = x + self_attn(hidden_states=input_layernorm(x), **kwargs)[0];   out = r1 + mlp(post_attention_layernorm(r1))
+
+    with each of the four children called once, every keyword argument of the layer handed to the attention unchanged, no other submodule touched and a tensor
+    returned.  Probed, not pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a tiny CPU tensor, and its result
+    must EQUAL the formula.  transformers' Llama, Mistral, Qwen2 and Qwen3 layers pass; Granite (residual_multiplier != 1), Gemma-2 and OLMo-2 (post-norms),
+    Phi-3 (dropout children), Cohere (parallel block) and any forward that raises on the stand-in do not."""
+    cls = cls or type(layer)
+    try:
+        names, var_kw = _forward_extra_params(cls)
+    except (TypeError, ValueError, AttributeError):
+        return False
+    given = {n: object() for n in names}
+    if var_kw:
+        given["pq_probe_extra"] = object()
+    calls = {c: 0 for c in _CHILDREN}
+    seen = {}
+
+    def norm1(t):
+        calls["input_layernorm"] += 1
+        return t * 2.0
+
+    def attn(*a, **kw):
+        calls["self_attn"] += 1
+        by_name = "hidden_states" in kw
+        h = kw.pop("hidden_states") if by_name else a[0]
+        seen["positional"], seen["kwargs"] = len(a) - (0 if by_name else 1), kw
+        return h + 1.0, None
+
+    def norm2(t):
+        calls["post_attention_layernorm"] += 1
+        return t * 0.5 - 3.0
+
+    def mlp(t):
+        calls["mlp"] += 1
+        return t * t
+
+    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
+    probe = _ProbeLayer(layer, {"input_layernorm": norm1, "self_attn": attn, "post_attention_layernorm": norm2, "mlp": mlp})
+    try:
+        with torch.no_grad():
+            out = cls.forward(probe, x.clone(), **given)
+    except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
+        return False
+    if not isinstance(out, torch.Tensor) or any(n != 1 for n in calls.values()):
+        return False
+    kw = seen["kwargs"]
+    if seen["positional"] != 0 or set(kw) != set(given) or any(kw[k] is not given[k] for k in given):
+        return False
+    r1 = x + (x * 2.0 + 1.0)
+    want = r1 + (r1 * 0.5 - 3.0) ** 2
+    return out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+
+
+class _HandOver:
+    """The quantised input one layer computed for the next (K1a's second use per layer), keyed by the identity of the tensor it belongs to and that tensor's version
+    counter.  take() empties it whatever the outcome; a copy — deep or pickled — starts empty."""
+    __slots__ = ("_key", "_version", "_q")
+
+    def __init__(self):
+        self.clear()
+
+    @staticmethod
+    def _version_of(t):
+        try:
+            return t._version
+        except Exception:          # noqa: BLE001  (inference tensors track no version counter)
+            return None
+
+    def put(self, key: torch.Tensor, q: QTensor):
+        self._key, self._version, self._q = key, self._version_of(key), q
+
+    def take(self, x):
+        key, version, q = self._key, self._version, self._q
+        self.clear()
+        return q if key is not None and key is x and version == self._version_of(x) else None
+
+    def clear(self):
+        self._key, self._version, self._q = None, None, None
+
+    @property
+    def pending(self) -> bool:
+        return self._key is not None
+
+    def __deepcopy__(self, memo):
+        return _HandOver()
+
+    def __reduce__(self):
+        return (_HandOver, ())
+
+
+class ResidualFusedLayer(nn.Module):
+    """A Llama-flow decoder layer whose two residual adds run inside the RMSNorm + quantisation kernels that follow them (K1a, add_rmsnorm_quantize):
+
+        h          = the QTensor handed over for this very tensor, else input_layernorm(hidden)
+        attn_out   = self_attn(hidden_states=h, **kwargs)[0]
+        hq, resid  = post_attention_layernorm(attn_out, residual=hidden)         # add + norm + quant, one launch
+        m          = mlp(hq)
+        last of the chain:  return resid + m                                     # a torch add
+        otherwise:          hq2, out = NEXT layer's input_layernorm(m, residual=resid);  hand hq2 to the next layer;  return out
+
+    What the layer returns is the real summed tensor (the bits of the two torch adds: QSPEC A1), so hooks, output_hidden_states and the final norm see what they saw.
+    fuse_llama_layers(fuse_residual=True) makes a layer one by giving the layer object a class that derives from this one AND from its original class: the object, its
+    four children under their names (state_dict keys), its other attributes, its hooks and every isinstance check on it stay as they were.  The tensor the layer was
+    called with is never written; the hand-over is consumed at the next layer's entry and never served for another tensor or a tensor changed in place since."""
+
+    def forward(self, hidden_states, *args, **kwargs):
+        if args:          # positional arguments of the original forward, by its own parameter names
+            if len(args) > len(self._rf_argnames):
+                raise TypeError(f"{type(self).__name__}.forward takes at most {len(self._rf_argnames) + 1} positional arguments")
+            kwargs.update(zip(self._rf_argnames, args))
+        h = self._rf_inbox.take(hidden_states)
+        if h is None:
+            h = self.input_layernorm(hidden_states)
+        attn_out = self.self_attn(hidden_states=h, **kwargs)[0]
+        hq, resid = self.post_attention_layernorm(attn_out, residual=hidden_states)
+        m = self.mlp(hq)
+        nxt = self._rf_next[0]
+        if nxt is None:
+            return resid + m
+        hq2, out = nxt.input_layernorm(m, residual=resid)
+        nxt._rf_inbox.put(out, hq2)
+        return out
+
+
+_RF_CLASSES: dict = {}
+
+
+def _residual_fused_class(cls):
+    if cls not in _RF_CLASSES:
+        _RF_CLASSES[cls] = type("ResidualFused" + cls.__name__, (ResidualFusedLayer, cls), {"__doc__": ResidualFusedLayer.__doc__})
+    return _RF_CLASSES[cls]
+
+
+def _rf_clear_hook(mod, args, output):
+    for layer in mod._rf_layers:          # (looked up on the module, not captured: a deep copy of the model clears its own layers)
+        layer._rf_inbox.clear()
+
+
+def _fuse_residual(model: nn.Module) -> int:
+    n = 0
+    for owner in list(model.modules()):
+        for _, stack in list(owner.named_children()):
+            if not isinstance(stack, nn.ModuleList):
+                continue
+            fresh = []
+            for layer in stack:
+                if isinstance(layer, ResidualFusedLayer) or not all(hasattr(layer, c) for c in _CHILDREN):
+                    continue
+                if not (isinstance(layer.input_layernorm, RMSNormQuant) and isinstance(layer.post_attention_layernorm, RMSNormQuant)):
+                    continue
+                cls = type(layer)
+                if not residual_flow_is_llama(layer, cls):
+                    continue
+                layer._rf_argnames = _forward_extra_params(cls)[0]
+                layer._rf_inbox, layer._rf_next = _HandOver(), [None]
+                layer.__class__ = _residual_fused_class(cls)
+                fresh.append(layer)
+            # (re)link the chain: a layer hands over to its successor in the stack when that one is residual-fused too; anything else ends the chain with a torch add
+            for i, layer in enumerate(stack):
+                if isinstance(layer, ResidualFusedLayer):
+                    nxt = stack[i + 1] if i + 1 < len(stack) else None
+                    layer._rf_next = [nxt if isinstance(nxt, ResidualFusedLayer) else None]          # (a list: the next layer is registered once, in the stack)
+            if fresh:
+                if not hasattr(owner, "_rf_layers"):
+                    owner._rf_layers = []
+                    owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
+                owner._rf_layers.extend(fresh)
+                n += len(fresh)
+    return n
+
+
+def residual_fused_layers(model: nn.Module) -> int:
+    """the number of ResidualFusedLayer modules in `model` (what fuse_llama_layers(fuse_residual=True) made, over all calls)"""
+    return sum(1 for m in model.modules() if isinstance(m, ResidualFusedLayer))
+
+
+def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool = True, fuse_residual: bool = False) -> int:
+    """Apply the fusions above to every decoder layer found in `model` (in place); returns the number of layers changed.
+
+    fuse_residual=True (opt-in; the default leaves everything as it was): afterwards, every layer of a ModuleList whose two norms are RMSNormQuant and whose class's
+    forward passes residual_flow_is_llama becomes a ResidualFusedLayer.  A refused layer keeps the fusions above and breaks the chain (its predecessor ends with a
+    torch add).  The module that owns the ModuleList gets an always-called forward hook that drops every pending hand-over when its forward ends.  The return value
+    is unchanged; residual_fused_layers(model) counts the residual-fused layers.  (shard_llama_layers is not covered: its residual stream is replicated over the ranks
+    and its layers keep the torch adds.)"""
     n = 0
     for layer in model.modules():
         attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
@@ -110,6 +334,8 @@ def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
         if fuse_norms and _is_rmsnorm(layer.post_attention_layernorm) and mlp_ok:
             layer.post_attention_layernorm = RMSNormQuant(layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon)
         n += 1
+    if fuse_residual:
+        _fuse_residual(model)
     return n
 
 

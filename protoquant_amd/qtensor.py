@@ -241,6 +241,55 @@ def rmsnorm_quantize(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, r
     return (qt, h.reshape(x.shape)) if return_h else qt
 
 
+def _rows_view_of_out(out: torch.Tensor, rows: int, cols: int, what: str) -> torch.Tensor:
+    """the 2-D [rows, cols] view of a destination tensor — a VIEW (never a copy: the kernel writes through it) with unit column stride"""
+    try:
+        o2 = out if out.dim() == 2 else out.view(rows, cols)
+    except RuntimeError:
+        o2 = None
+    if o2 is None or (cols > 1 and o2.stride(1) != 1) or (rows > 1 and o2.stride(0) < cols):
+        raise ValueError(f"{what}: out must be viewable as [{rows}, {cols}] rows with contiguous columns, got strides {tuple(out.stride())}")
+    return o2
+
+
+def add_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, out: torch.Tensor | None = None, return_h: bool = False):
+    """summed = residual + x, then rmsnorm_quantize(summed, weight, eps) — in ONE kernel (K1a): the new residual stream is stored once and normalised, reduced and
+    encoded from the registers that hold it.  Returns (QTensor, summed) or (QTensor, summed, h) with return_h=True; every one of them holds the bits of
+    rmsnorm_quantize(residual + x, weight, eps, return_h=True) with the add done by torch (QSPEC A1: one binary32 add, one storage rounding, then N1-N6, Q1-Q6).
+    x and residual have the same shape, dtype and device.  `out` (optional, the same shape and dtype) receives the sum and may be x or residual themselves; any
+    other tensor that overlaps an input is refused.  `summed` has x's shape."""
+    L.require_gpu(x, "add_rmsnorm_quantize(x)")
+    L.require_gpu(residual, "add_rmsnorm_quantize(residual)")
+    L.require_gpu(weight, "add_rmsnorm_quantize(weight)")
+    if x.dim() < 1 or x.shape != residual.shape or x.dtype != residual.dtype or x.device != residual.device:
+        raise ValueError(f"add_rmsnorm_quantize: x {tuple(x.shape)} {x.dtype} {x.device} and residual {tuple(residual.shape)} {residual.dtype} {residual.device} must match")
+    if weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"add_rmsnorm_quantize: x {tuple(x.shape)} {x.dtype} needs a weight of shape ({x.shape[-1]},) and the same dtype/device, "
+                         f"got {tuple(weight.shape)} {weight.dtype}")
+    if out is not None:
+        L.require_gpu(out, "add_rmsnorm_quantize(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"add_rmsnorm_quantize: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, "add_rmsnorm_quantize")
+    if rows == 0 or cols == 0:          # nothing to add: the empty sum through K1n (scales of empty rows are 1, QSPEC Q3)
+        res = rmsnorm_quantize(summed, weight, eps, return_h)
+        return (res[0], summed, res[1]) if return_h else (res, summed)
+    w = weight.contiguous()
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_add_rmsnorm_quant_rowwise(x2.data_ptr(), L.ld(x2), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2), w.data_ptr(), float(eps), code, rows, cols,
+                                                     q.data_ptr(), cols, scale.data_ptr(), h.data_ptr() if return_h else None, cols, L.stream_ptr(x)),
+                "add_rmsnorm_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
+
+
 def dequantize(q: QTensor, dtype: torch.dtype | None = None) -> torch.Tensor:
     """cast_rne(f32(int_data) * scale) along the kept axis -> `dtype` (default: the original dtype)."""
     dtype = dtype or q.orig_dtype
