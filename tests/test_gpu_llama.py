@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import c_oracle as C
+from tests import llama_twin
 from tests.gpu_util import bits, same
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +36,12 @@ def test_fused_llama_layers_match_unfused_and_oracle(pq):
     nw = l0.input_layernorm.weight.detach().cpu().clone()
     pq.swap_linears(model, fuse_gated_mlp=True)
     unfused = copy.deepcopy(model)
+    twin = llama_twin.twin(model)          # the unfused model with the QSPEC norm in place of HF's: what the fused model equals in every bit (tests/llama_twin.py)
     assert fuse_llama_layers(model) == 2
     assert isinstance(model.model.layers[0].input_layernorm, RMSNormQuant) and isinstance(model.model.layers[1].post_attention_layernorm, RMSNormQuant)
     ids = torch.randint(0, 512, (2, 96), device="cuda")
     with torch.no_grad():
-        a, b = unfused(ids).logits, model(ids).logits
+        a, b, t = unfused(ids).logits, model(ids).logits, twin(ids).logits
     # What the fused model IS: QSPEC-exact — N1-N6 pin one summation order for the mean of squares — and eager-CLOSE: HF's LlamaRMSNorm sums in torch's
     # order, so about 5e-6 of the stored bf16 activations (at most 2 ulp) and 7e-7 of the codes differ between the fused and the eager chain (measured and bounded at
     # H = 4096 / 8192 on 10^7 elements: tests/test_gpu_rmsnorm_vs_eager.py).  On this toy (4 norms x 192 rows x 256 columns) that is ~1 activation in expectation: the logits
@@ -47,6 +49,7 @@ def test_fused_llama_layers_match_unfused_and_oracle(pq):
     # The bit-exact statements are the ones below: the fused norm + qkv against the C oracle's N1-N6 chain.
     assert torch.allclose(a.float(), b.float(), rtol=3e-2, atol=3e-2), float((a.float() - b.float()).abs().max())
     assert (a.view(torch.int16) != b.view(torch.int16)).float().mean().item() < 0.5
+    assert torch.equal(t, b), "the fused model differs from its unfused twin with the QSPEC norm"          # (every family, dtype and geometry: tests/test_gpu_llama_bits.py)
     # layer 0's fused norm + qkv against the oracle chain
     x = torch.randn(50, 256, device="cuda").to(torch.bfloat16)
     with torch.no_grad():
@@ -68,8 +71,11 @@ def test_fused_llama_layers_match_unfused_and_oracle(pq):
         b2, a2 = model(ids).logits, None
         unfused.model.embed_tokens.weight.mul_(2.0)
         a2 = unfused(ids).logits
+        twin.model.embed_tokens.weight.mul_(2.0)
+        t2 = twin(ids).logits
     assert torch.equal(b1.view(torch.int16), b.view(torch.int16))                  # the same fused model, the same input: the same bits
     assert not torch.equal(b2.view(torch.int16), b1.view(torch.int16)) and torch.allclose(a2.float(), b2.float(), rtol=3e-2, atol=3e-2)      # fresh results, eager-close (see above)
+    assert torch.equal(t2, b2)                                                     # ... and the twin's bits
     assert all(l.self_attn.qkv_fused._outs is None and l.self_attn.qkv_fused._key is None for l in model.model.layers)
     # a deep copy of the fused model shares nothing with the original: its attention hooks drive its own fused GEMM
     clone = copy.deepcopy(model)

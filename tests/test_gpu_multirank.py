@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import warnings
 
 import pytest
 import torch
@@ -98,12 +99,22 @@ def _bench_tp(extra, port, hooks="", cpu_baseline=False, env_extra=None, _retrie
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "tp", "--steps", "6", "--warmup", "2", "--repeats", "3", "--warmup-seconds", "0.3",
                         *([] if cpu_baseline else ["--no-cpu-baseline"]), "--no-dp-leg", *extra], env=env, capture_output=True, text=True, timeout=600)
-    if r.returncode != 0 and "bad_variant_access" in r.stderr and not _retried:
-        # torch.distributed's own start-up died once in ~40 runs of round 6 with `std::bad_variant_access` before the communicator existed (0 of 160 in tools/init_stress.py):
-        # not this repository's code, so one retry keeps the suite from failing on it — a second failure is reported
-        return _bench_tp(extra, port, hooks, cpu_baseline, env_extra, _retried=True)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    if _died_in_startup(r.returncode, r.stdout, r.stderr) and not _retried:
+        # torch.distributed's own start-up died once in ~40 runs of round 6 with `std::bad_variant_access` before the communicator existed (0 of 160 in tools/init_stress.py):
+        # not this repository's code, so one retry keeps the suite from failing on it — visibly (the flake rate stays countable), on another port, and ONLY when the run
+        # left nothing behind: a crash after start-up, whatever exception it names, is this repository's to explain and fails the test
+        warnings.warn(f"bench.py --mode tp died inside torch.distributed's start-up (exit {r.returncode}, std::bad_variant_access, no line printed): retrying once", stacklevel=2)
+        return _bench_tp(extra, str(int(port) + 100), hooks, cpu_baseline, env_extra, _retried=True)
     return r, lines
+
+
+def _died_in_startup(returncode: int, stdout: str, stderr: str) -> bool:
+    """True iff a failed bench.py --mode tp run ended before init_process_group returned: the known start-up exception, and neither a JSON line on stdout nor one of
+    bench.py's own `[bench]` marker lines on stderr (every leg, watchdog, supervisor and warning path prints one): nothing of this repository had run yet."""
+    if returncode == 0 or "bad_variant_access" not in stderr:
+        return False
+    return not any(l.startswith("{") for l in stdout.splitlines()) and "[bench]" not in stderr
 
 
 def test_bench_tp_watchdog_prints_the_best_finished_leg_when_a_native_leg_hangs():

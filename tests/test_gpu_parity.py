@@ -297,10 +297,16 @@ def test_fused_splitk_matches(pq, M, N, S, NT, code, bias, pq_opt):
     assert torch.equal(out.view(torch.uint8), y_def.view(torch.uint8)), "cooperative fused split-K under capture"
 
 
-@pytest.mark.parametrize("M,N,S,NT", [(300, 300, 3, 17), (520, 260, 3, 64), (260, 300, 5, 27), (4096, 1280, 3, 64), (300, 520, 7, 36)])
+@pytest.mark.parametrize("M,N,S,NT", [(300, 300, 3, 17), (520, 260, 3, 64), (260, 300, 5, 27), (4096, 1280, 3, 64), (300, 520, 7, 36),
+                                      (300, 300, 2, 17), (520, 260, 4, 27), (2048, 1024, 2, 43), (1024, 1024, 4, 27), (260, 300, 4, 23)])
 def test_fused_splitk_with_uneven_slices(pq, pq_opt, M, N, S, NT):
     """round 6: the ticket form deals the K-tiles as evenly as they go — NT K-tiles over S slices, the first NT % S slices one more (3 slices of 64: 22 / 21 / 21; 5 of 27: 6 / 6 / 5 / 5 / 5,
-    the minimum of five per slice) — where rounds 3-5 wanted K % (128 S) == 0.  Bit-identical to the single-pass dispatch and (small shapes) to the oracle, repeated on one workspace."""
+    the minimum of five per slice) — where rounds 3-5 wanted K % (128 S) == 0.  Bit-identical to the single-pass dispatch and (small shapes) to the oracle, repeated on one workspace.
+    S = 2 and 4 (17 -> 9 / 8, 27 -> 7 / 7 / 7 / 6, 23 -> 6 / 6 / 6 / 5, 43 -> 22 / 21) are the slice counts the SYMMETRIC kernels exist for: the ticket form runs them uneven by default, and PQ_FSK_COOP=1
+    launches gemm_s8_sp256<FSK = 2 / 4> cooperatively WITH those uneven slices (fsk_plan stopped asking for K % (128 S) == 0 unless PQ_FSK_SYMMETRIC is set).  The kernel
+    admits it: a workgroup's K range (kt_start, Ks) follows from its own slice index alone, and the exchange (fsk_sym2_asm / fsk_sym4_asm) runs behind the K-loop on regions and
+    flags indexed by (tile, writer slice, reader slice) — nothing in it knows a tile count; the partner with fewer K-tiles only polls a little longer, and the cooperative launch
+    keeps it resident meanwhile.  Four repetitions per form on ONE workspace (the launcher re-zeroes the flags)."""
     from protoquant_amd import _lib
     K = NT * 128
     assert K % (128 * S) != 0
@@ -320,6 +326,12 @@ def test_fused_splitk_with_uneven_slices(pq, pq_opt, M, N, S, NT):
     for rep in range(4):
         y = pq.qlinear_s8(*args)
         assert torch.equal(y.view(torch.uint8), y_def.view(torch.uint8)), f"uneven fused split-K y (rep {rep})"
+    if S in (2, 4):
+        pq_opt("PQ_FSK_COOP", "1")                       # the symmetric exchange between partners with DIFFERENT tile counts, under the runtime's co-residency guarantee
+        for rep in range(4):
+            y = pq.qlinear_s8(*args)
+            assert torch.equal(y.view(torch.uint8), y_def.view(torch.uint8)), f"uneven cooperative fused split-K y (rep {rep})"
+        pq_opt("PQ_FSK_COOP", "")
     pq_opt("PQ_FSK_SYMMETRIC", "1")                      # the symmetric forms keep equal slices: an uneven K is refused by that plan (the planner's other choices run): same bits
     assert torch.equal(pq.qlinear_s8(*args).view(torch.uint8), y_def.view(torch.uint8))
 
