@@ -137,6 +137,39 @@ int32_t pq_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight
 int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
                                      int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
 
+/* K1l — K1 fused into LayerNorm (GPT-2, StarCoder2, GPT-NeoX, Falcon, Phi, OPT and the encoders): quantize(LayerNorm(x; weight, bias, eps)) per token in one pass,
+ * the normalised activation never reaching HBM unless h_out asks for it.  x: [rows, cols], weight: [cols], bias: [cols] or NULL (no bias, no add), all of `dtype`.
+ * Numerics, QSPEC L1-L6, all binary32, round to nearest even, no contraction: mean = (sum x) / cols and var = (sum (x - mean)^2) / cols, a true
+ * two-pass computation, both sums in the pinned order of pq_rmsnorm_quant_rowwise (16-byte vectors dealt to 256 lanes, per lane a plain add resp. an fma per element,
+ * xor butterfly per 64 lanes, four partial sums left to right: every row layout gives the same bits); rs = 1 / sqrt(var + eps) with IEEE sqrt and division;
+ * h = cast_rne(((x - mean) * rs) * weight + bias), every operation rounded in binary32 and ONE storage rounding (what torch's layer_norm does on a 16-bit tensor;
+ * pq_rmsnorm_quant_rowwise rounds twice because transformers' RMSNorm does); then Q1-Q6 on the rows of h.  A NaN or Inf anywhere in a row makes the whole row NaN
+ * (scale = the canonical NaN, codes 0).
+ * q, scale and h_out may overlap neither x, weight, bias nor each other (PQ_ERR_BAD_ARG: an in-place h_out is not tolerated, the layouts re-read clamped duplicates
+ * of x).  A null x / weight / q / scale, ld < cols, cols >= 2^24, a negative or non-finite eps and an unknown dtype are PQ_ERR_BAD_ARG before any HIP call, with
+ * pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or written, returns PQ_OK.  Row layouts and the PQ_RMS_WAVE_MAX switch as
+ * pq_rmsnorm_quant_rowwise (time only, never bits). */
+int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, const void* bias, float eps, int32_t dtype, int64_t rows, int64_t cols,
+                                   int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
+/* K1u — K1 fused into the unary activation of a plain two-linear MLP (c_proj(act(c_fc(x)))): quantize(act(x)) per token in one pass.  x: [rows, cols] of `dtype`,
+ * possibly a column block of a wider tensor (ld_x > cols).  Numerics, QSPEC U1-U4, binary32 throughout and ONE storage rounding of h:
+ *   PQ_ACT_RELU       h = x < 0 ? +0 : x                        (a NaN and -0 pass: torch.relu, bit for bit)
+ *   PQ_ACT_GELU_TANH  h = x / (1 + exp_spec(-a)), a = x * fma(x * x, K1, K0), K0 = 2 sqrt(2 / pi), K1 = 0.044715 K0   (the tanh GELU without its 1 + tanh
+ *                     cancellation: 0.5 x (1 + tanh(u)) = x / (1 + exp(-2 u)))
+ *   PQ_ACT_GELU_ERF   h = x * Phi(x), Phi(x) = 0.5 erfc(-x / sqrt 2) from a specified binary32 sequence (a degree-10 polynomial of (t - 4) / (t + 4), t = min(|x|, 12),
+ *                     times exp_spec(-t^2 / 8)^4)
+ * exp_spec is QSPEC S1-S4.  Both GELUs are within 1 ulp of the storage dtype of the exact value for every bf16 / fp16 input (exact values below 2^-96 become -0);
+ * NaN -> NaN, +Inf -> +Inf, -Inf -> -0.  Then Q1-Q6 on the rows of h.  h_out (nullable, ld_h): also store h.
+ * q, scale and h_out may overlap neither x nor each other.  An unknown kind or dtype, a null x / q / scale, negative sizes and ld < cols are PQ_ERR_BAD_ARG before any
+ * HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or written, returns PQ_OK.  Row layouts as pq_silu_mul_quant_rowwise
+ * (PQ_SILU_TPR included: time only, never bits). */
+#define PQ_ACT_RELU 0
+#define PQ_ACT_GELU_TANH 1
+#define PQ_ACT_GELU_ERF 2
+int32_t pq_act_quant_rowwise(const void* x, int64_t ld_x, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q, float* scale,
+                             void* h_out, int64_t ld_h, void* stream);
+
 /* dequantize(): out[r,c] = cast_rne(f32(q[r,c]) * scale[axis==0 ? c : r]).  `axis` is the axis the
  * scale was reduced over (1: one scale per row, 0: one scale per column).   QSPEC D1. */
 int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t axis,

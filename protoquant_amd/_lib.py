@@ -14,6 +14,7 @@ ABI_VERSION = 1
 
 PQ_BF16, PQ_FP16, PQ_F32 = 0, 1, 2
 GLU_KINDS = {"clamped_silu": 0, "alpha_sigmoid": 1}        # PQ_GLU_* of include/pq_hip.h
+ACT_KINDS = {"relu": 0, "gelu_tanh": 1, "gelu_erf": 2}     # PQ_ACT_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
 EXPORTS = (
@@ -28,6 +29,7 @@ EXPORTS = (
     "pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine",
     "pq_glu_quant_rowwise", "pq_selftest_glu_short",
     "pq_add_rmsnorm_quant_rowwise",
+    "pq_layernorm_quant_rowwise", "pq_act_quant_rowwise",
 )
 
 _lib = None
@@ -116,6 +118,10 @@ def lib() -> ctypes.CDLL:
     L.pq_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_add_rmsnorm_quant_rowwise.restype = i32
     L.pq_add_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_layernorm_quant_rowwise.restype = i32
+    L.pq_layernorm_quant_rowwise.argtypes = [vp, i64, vp, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_act_quant_rowwise.restype = i32
+    L.pq_act_quant_rowwise.argtypes = [vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
     L.pq_set_option.restype = i32
     L.pq_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     L.pq_selftest_fast_quotient.restype = i32

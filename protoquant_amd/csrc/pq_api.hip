@@ -43,6 +43,8 @@ void launch_silu_short_check(int, unsigned long long*, hipStream_t);
 template <int DT> void glu_quant_dispatch(int, const void*, int64_t, const void*, int64_t, int64_t, int64_t, float, float, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 float glu_limit_in_dtype(int, float);
 void launch_glu_short_check(int, int, float, float, unsigned long long*, hipStream_t);
+template <int DT> void layernorm_quant_dispatch(const void*, int64_t, const void*, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+template <int DT> void act_quant_dispatch(int, const void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 }  // namespace pq
 
 namespace {
@@ -594,6 +596,79 @@ int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* re
         case PQ_BF16: pq::add_rmsnorm_quant_dispatch<PQ_BF16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
         case PQ_FP16: pq::add_rmsnorm_quant_dispatch<PQ_FP16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
         default: pq::add_rmsnorm_quant_dispatch<PQ_F32>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+    }
+    return check_launch(fn);
+}
+
+// The outputs of the two LayerNorm-family producers (K1l, K1u) may overlap neither an input nor each other: the vector layouts load a clamped duplicate of a row's
+// last vector into the slots past its end and the generic kernels read x again in every pass, so an in-place h_out is not tolerated.  nullptr = fine.
+namespace {
+struct NamedExtent { const char* name; Extent e; };
+const char* first_overlap(const NamedExtent* ins, int nin, const NamedExtent* outs, int nout, char* buf, size_t nbuf) {
+    for (int o = 0; o < nout; ++o) {
+        for (int i = 0; i < nin; ++i)
+            if (extents_overlap(outs[o].e, ins[i].e)) { snprintf(buf, nbuf, "%s overlaps %s", outs[o].name, ins[i].name); return buf; }
+        for (int o2 = o + 1; o2 < nout; ++o2)
+            if (extents_overlap(outs[o].e, outs[o2].e)) { snprintf(buf, nbuf, "%s overlaps %s", outs[o].name, outs[o2].name); return buf; }
+    }
+    return nullptr;
+}
+}  // namespace
+
+int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, const void* bias, float eps, int32_t dtype, int64_t rows, int64_t cols,
+                                   int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:layernorm_quant (K1l)");
+    const char* fn = "pq_layernorm_quant_rowwise";
+    if (dtype < 0 || dtype > 2) return fail(PQ_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (rows < 0 || cols < 0 || cols >= (1 << 24)) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld; cols < 2^24)", fn, (long long)rows, (long long)cols);
+    if (!(eps >= 0.0f) || eps > 3.4028234e38f) return fail(PQ_ERR_BAD_ARG, "%s: eps must be finite and >= 0 (eps=%g)", fn, (double)eps);
+    if (ld_x < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_x %lld < cols %lld", fn, (long long)ld_x, (long long)cols);
+    if (ld_q < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_q %lld < cols %lld", fn, (long long)ld_q, (long long)cols);
+    if (h_out && ld_h < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_h %lld < cols %lld", fn, (long long)ld_h, (long long)cols);
+    if (rows == 0 || cols == 0) return PQ_OK;
+    if (!x) return fail(PQ_ERR_BAD_ARG, "%s: x is null", fn);
+    if (!weight) return fail(PQ_ERR_BAD_ARG, "%s: weight is null (a LayerNorm without affine parameters is not supported)", fn);
+    if (!q) return fail(PQ_ERR_BAD_ARG, "%s: q is null", fn);
+    if (!scale) return fail(PQ_ERR_BAD_ARG, "%s: scale is null", fn);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const NamedExtent ins[] = {{"x", extent_of(x, ld_x, rows, cols, eb)}, {"weight", extent_of(weight, cols, 1, cols, eb)}, {"bias", extent_of(bias, cols, 1, cols, eb)}};
+    const NamedExtent outs[] = {{"q", extent_of(q, ld_q, rows, cols, 1)}, {"scale", extent_of(scale, rows, 1, rows, 4)}, {"h_out", extent_of(h_out, ld_h, rows, cols, eb)}};
+    char why[64];
+    if (first_overlap(ins, 3, outs, 3, why, sizeof why)) return fail(PQ_ERR_BAD_ARG, "%s: %s", fn, why);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case PQ_BF16: pq::layernorm_quant_dispatch<PQ_BF16>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        case PQ_FP16: pq::layernorm_quant_dispatch<PQ_FP16>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        default: pq::layernorm_quant_dispatch<PQ_F32>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+    }
+    return check_launch(fn);
+}
+
+int32_t pq_act_quant_rowwise(const void* x, int64_t ld_x, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q, float* scale,
+                             void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:act_quant (K1u)");
+    const char* fn = "pq_act_quant_rowwise";
+    if (dtype < 0 || dtype > 2) return fail(PQ_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (kind != PQ_ACT_RELU && kind != PQ_ACT_GELU_TANH && kind != PQ_ACT_GELU_ERF)
+        return fail(PQ_ERR_BAD_ARG, "%s: unknown kind %d (0 = relu, 1 = gelu_tanh, 2 = gelu_erf)", fn, kind);
+    if (rows < 0 || cols < 0) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld)", fn, (long long)rows, (long long)cols);
+    if (ld_x < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_x %lld < cols %lld", fn, (long long)ld_x, (long long)cols);
+    if (ld_q < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_q %lld < cols %lld", fn, (long long)ld_q, (long long)cols);
+    if (h_out && ld_h < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_h %lld < cols %lld", fn, (long long)ld_h, (long long)cols);
+    if (rows == 0 || cols == 0) return PQ_OK;
+    if (!x) return fail(PQ_ERR_BAD_ARG, "%s: x is null", fn);
+    if (!q) return fail(PQ_ERR_BAD_ARG, "%s: q is null", fn);
+    if (!scale) return fail(PQ_ERR_BAD_ARG, "%s: scale is null", fn);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const NamedExtent ins[] = {{"x", extent_of(x, ld_x, rows, cols, eb)}};
+    const NamedExtent outs[] = {{"q", extent_of(q, ld_q, rows, cols, 1)}, {"scale", extent_of(scale, rows, 1, rows, 4)}, {"h_out", extent_of(h_out, ld_h, rows, cols, eb)}};
+    char why[64];
+    if (first_overlap(ins, 1, outs, 3, why, sizeof why)) return fail(PQ_ERR_BAD_ARG, "%s: %s", fn, why);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case PQ_BF16: pq::act_quant_dispatch<PQ_BF16>(kind, x, ld_x, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        case PQ_FP16: pq::act_quant_dispatch<PQ_FP16>(kind, x, ld_x, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        default: pq::act_quant_dispatch<PQ_F32>(kind, x, ld_x, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
     }
     return check_launch(fn);
 }

@@ -290,6 +290,61 @@ def add_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torch.
     return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
 
 
+def layernorm_quantize(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, eps: float = 1e-5, return_h: bool = False):
+    """quantize(F.layer_norm(x, (C,), weight, bias, eps), axis=-1) in ONE pass (kernel K1l: K1 fused into LayerNorm): the normalised activation feeding c_attn /
+    q, k, v / c_fc is reduced, normalised and encoded in registers.  `weight` is required (a LayerNorm without affine parameters is refused); `bias` may be None.
+    Numerics: QSPEC L1-L6 (two-pass mean and variance in a pinned reduction order, one storage rounding) then Q1-Q6.  return_h=True also returns the normalised
+    activation in the input dtype (stored by the same kernel)."""
+    L.require_gpu(x, "layernorm_quantize(x)")
+    if weight is None:
+        raise ValueError("layernorm_quantize: weight is None — a LayerNorm without affine parameters (elementwise_affine=False) is not supported")
+    L.require_gpu(weight, "layernorm_quantize(weight)")
+    if x.dim() < 1 or weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"layernorm_quantize: x {tuple(x.shape)} {x.dtype} needs a weight of shape ({x.shape[-1] if x.dim() else '?'},) "
+                         f"and the same dtype/device, got {tuple(weight.shape)} {weight.dtype}")
+    if bias is not None:
+        L.require_gpu(bias, "layernorm_quantize(bias)")
+        if bias.shape != weight.shape or bias.dtype != x.dtype or bias.device != x.device:
+            raise ValueError(f"layernorm_quantize: bias {tuple(bias.shape)} {bias.dtype} must match the weight {tuple(weight.shape)} {weight.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2 = _rows_view(x)
+    w = weight.contiguous()
+    b = bias.contiguous() if bias is not None else None
+    rows, cols = x2.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device) if cols > 0 else torch.ones((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_layernorm_quant_rowwise(x2.data_ptr(), L.ld(x2), w.data_ptr(), b.data_ptr() if b is not None else None, float(eps), code, rows, cols,
+                                                   q.data_ptr(), max(cols, 1), scale.data_ptr(), h.data_ptr() if return_h else None, max(cols, 1),
+                                                   L.stream_ptr(x)), "layernorm_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, h.reshape(x.shape)) if return_h else qt
+
+
+def act_quantize(x: torch.Tensor, kind: str, return_h: bool = False):
+    """quantize(act(x), axis=-1) in ONE pass (kernel K1u) for the unary activation of a plain two-linear MLP: kind "relu" (torch.relu), "gelu_tanh" (gelu_new,
+    gelu_pytorch_tanh) or "gelu_erf" (F.gelu's default).  x may be a column slice of a wider tensor.  Numerics: QSPEC U1-U4 then Q1-Q6 — relu holds torch's bits;
+    both GELUs are within 1 ulp of the input dtype of the exact value, closer to it than torch's eager kernels are, and not bit-identical to those.
+    return_h=True also returns h = act(x) in the input dtype (stored by the same kernel)."""
+    L.require_gpu(x, "act_quantize(x)")
+    if kind not in L.ACT_KINDS:
+        raise ValueError(f"act_quantize: unknown kind {kind!r}, expected one of {sorted(L.ACT_KINDS)}")
+    if x.dim() < 1:
+        raise ValueError("act_quantize: x needs at least 1 dimension")
+    code = L.dtype_code(x.dtype)
+    x2 = _rows_view(x)
+    rows, cols = x2.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device) if cols > 0 else torch.ones((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_act_quant_rowwise(x2.data_ptr(), L.ld(x2), code, rows, cols, L.ACT_KINDS[kind], q.data_ptr(), max(cols, 1), scale.data_ptr(),
+                                             h.data_ptr() if return_h else None, max(cols, 1), L.stream_ptr(x)), "act_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, h.reshape(x.shape)) if return_h else qt
+
+
 def dequantize(q: QTensor, dtype: torch.dtype | None = None) -> torch.Tensor:
     """cast_rne(f32(int_data) * scale) along the kept axis -> `dtype` (default: the original dtype)."""
     dtype = dtype or q.orig_dtype
