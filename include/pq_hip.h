@@ -152,6 +152,16 @@ int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* re
 int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, const void* bias, float eps, int32_t dtype, int64_t rows, int64_t cols,
                                    int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
 
+/* K1al — the residual add that precedes a LayerNorm in a decoder layer, fused into K1l: sum_out = x + residual (QSPEC A1: one binary32 add and one storage rounding
+ * per element — what an eager add stores), then pq_layernorm_quant_rowwise on the rows of sum_out AS STORED (L1-L6, Q1-Q6), in one kernel.  Every output holds the
+ * bits of the two-launch form.  x, residual, sum_out: [rows, cols] of `dtype` with leading dimensions ld_x, ld_r, ld_s (elements); weight, bias: [cols] of the same
+ * dtype, bias nullable.  sum_out is required and may be x or residual themselves (same pointer and leading dimension); any other overlap of sum_out with an input,
+ * and any overlap of q, scale or h_out with another operand, returns PQ_ERR_BAD_ARG — as do a null operand (bias and h_out excepted), ld < cols, cols >= 2^24, a
+ * negative or non-finite eps and an unknown dtype — before any HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or
+ * written, returns PQ_OK.  Row layouts and the PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time only, never bits). */
+int32_t pq_add_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, const void* bias,
+                                       float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* K1u — K1 fused into the unary activation of a plain two-linear MLP (c_proj(act(c_fc(x)))): quantize(act(x)) per token in one pass.  x: [rows, cols] of `dtype`,
  * possibly a column block of a wider tensor (ld_x > cols).  Numerics, QSPEC U1-U4, binary32 throughout and ONE storage rounding of h:
  *   PQ_ACT_RELU       h = x < 0 ? +0 : x                        (a NaN and -0 pass: torch.relu, bit for bit)

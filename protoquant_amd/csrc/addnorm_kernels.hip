@@ -9,22 +9,9 @@
 // Aliasing: sum_out may be exactly x or exactly residual (same base, same leading dimension; pq_api.hip refuses every other overlap).  A row belongs to one wave
 // or workgroup and a thread reads every element of x and of residual before it writes that element of the sum; the three pointers carry no __restrict__.  Slots
 // past the row's end (and the rows of inactive waves) load a clamped duplicate that another thread may be overwriting: they are zeroed before any use.
-#include "producer_device.h"
+#include "addnorm_device.h"
 
 namespace pq {
-
-// A1 on one 16-byte vector: one binary32 add per element (residual + x), then the storage rounding
-template <int DT>
-__device__ __forceinline__ v4u add_vec(const v4u& xv, const v4u& rv) {
-    v4u out;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t xw = xv[j], rw = rv[j];      // copies first (hipcc quirk with vector-element lvalues)
-        if constexpr (DT == PQ_F32) out[j] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, rw) + __builtin_bit_cast(float, xw));
-        else out[j] = Pair<DT>::pack(Pair<DT>::unpack(rw) + Pair<DT>::unpack(xw));
-    }
-    return out;
-}
 
 // An empty statement that takes every sum as an operand and clobbers memory: the loads written after it (the weight row) are issued after the adds, when the
 // residual's registers are free — hipcc otherwise hoists them above the adds and holds x, the residual and the weight at once (16 vectors: 256 VGPRs + AGPRs).

@@ -44,6 +44,7 @@ template <int DT> void glu_quant_dispatch(int, const void*, int64_t, const void*
 float glu_limit_in_dtype(int, float);
 void launch_glu_short_check(int, int, float, float, unsigned long long*, hipStream_t);
 template <int DT> void layernorm_quant_dispatch(const void*, int64_t, const void*, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+template <int DT> void add_layernorm_quant_dispatch(const void*, int64_t, const void*, int64_t, void*, int64_t, const void*, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 template <int DT> void act_quant_dispatch(int, const void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 }  // namespace pq
 
@@ -640,6 +641,46 @@ int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weig
         case PQ_BF16: pq::layernorm_quant_dispatch<PQ_BF16>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
         case PQ_FP16: pq::layernorm_quant_dispatch<PQ_FP16>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
         default: pq::layernorm_quant_dispatch<PQ_F32>(x, ld_x, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+    }
+    return check_launch(fn);
+}
+
+int32_t pq_add_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, const void* bias,
+                                       float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:add_layernorm_quant (K1al)");
+    const char* fn = "pq_add_layernorm_quant_rowwise";
+    if (dtype < 0 || dtype > 2) return fail(PQ_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (rows < 0 || cols < 0 || cols >= (1 << 24)) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld; cols < 2^24)", fn, (long long)rows, (long long)cols);
+    if (!(eps >= 0.0f) || eps > 3.4028234e38f) return fail(PQ_ERR_BAD_ARG, "%s: eps must be finite and >= 0 (eps=%g)", fn, (double)eps);
+    if (ld_x < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_x %lld < cols %lld", fn, (long long)ld_x, (long long)cols);
+    if (ld_r < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_r %lld < cols %lld", fn, (long long)ld_r, (long long)cols);
+    if (ld_s < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_s %lld < cols %lld", fn, (long long)ld_s, (long long)cols);
+    if (ld_q < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_q %lld < cols %lld", fn, (long long)ld_q, (long long)cols);
+    if (h_out && ld_h < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_h %lld < cols %lld", fn, (long long)ld_h, (long long)cols);
+    if (rows == 0 || cols == 0) return PQ_OK;
+    if (!x) return fail(PQ_ERR_BAD_ARG, "%s: x is null", fn);
+    if (!residual) return fail(PQ_ERR_BAD_ARG, "%s: residual is null", fn);
+    if (!sum_out) return fail(PQ_ERR_BAD_ARG, "%s: sum_out is null (the sum is the new residual stream: it is always stored)", fn);
+    if (!weight) return fail(PQ_ERR_BAD_ARG, "%s: weight is null (a LayerNorm without affine parameters is not supported)", fn);
+    if (!q) return fail(PQ_ERR_BAD_ARG, "%s: q is null", fn);
+    if (!scale) return fail(PQ_ERR_BAD_ARG, "%s: scale is null", fn);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const Extent ex = extent_of(x, ld_x, rows, cols, eb), er = extent_of(residual, ld_r, rows, cols, eb), es = extent_of(sum_out, ld_s, rows, cols, eb);
+    // sum_out may BE x or the residual (same base and pitch: every element is read before it is written, by the thread that writes it); any other overlap is refused
+    if (!(sum_out == x && ld_s == ld_x) && extents_overlap(es, ex)) return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps x without being x (same pointer and leading dimension)", fn);
+    if (!(sum_out == residual && ld_s == ld_r) && extents_overlap(es, er))
+        return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps residual without being residual (same pointer and leading dimension)", fn);
+    const NamedExtent ins[] = {{"x", ex}, {"residual", er}, {"weight", extent_of(weight, cols, 1, cols, eb)}, {"bias", extent_of(bias, cols, 1, cols, eb)}, {"sum_out", es}};
+    if (extents_overlap(es, ins[2].e)) return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps weight", fn);
+    if (extents_overlap(es, ins[3].e)) return fail(PQ_ERR_BAD_ARG, "%s: sum_out overlaps bias", fn);
+    const NamedExtent outs[] = {{"q", extent_of(q, ld_q, rows, cols, 1)}, {"scale", extent_of(scale, rows, 1, rows, 4)}, {"h_out", extent_of(h_out, ld_h, rows, cols, eb)}};
+    char why[64];
+    if (first_overlap(ins, 5, outs, 3, why, sizeof why)) return fail(PQ_ERR_BAD_ARG, "%s: %s", fn, why);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case PQ_BF16: pq::add_layernorm_quant_dispatch<PQ_BF16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        case PQ_FP16: pq::add_layernorm_quant_dispatch<PQ_FP16>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
+        default: pq::add_layernorm_quant_dispatch<PQ_F32>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); break;
     }
     return check_launch(fn);
 }

@@ -9,9 +9,13 @@ Pythia, and whatever else passes the same probes:
 
 ``swap_linears(model)`` must have run first.  Nothing is recognised by class name or by import: a block's own forward is run on the CPU against stand-ins
 (``_Standin``) whose projections are recorders, and a replacement happens only where that run shows the data flow the fused form needs.  A refusal leaves
-the module objects untouched.  Composes with ``fuse_llama_layers`` (StarCoder2's q / k / v) in either call order."""
+the module objects untouched.  Composes with ``fuse_llama_layers`` (StarCoder2's q / k / v) in either call order.
+
+``fuse_layernorm_residual(model)`` (opt-in, run after ``fuse_layernorm_layers``) also takes the two residual adds of a sequential pre-norm block into the LayerNorm that follows
+them (``add_layernorm_quantize``, kernel K1al: the residual stream is stored once and normalised from registers): see ``ResidualFusedBlock``."""
 from __future__ import annotations
 
+import copy
 import inspect
 import types
 
@@ -19,9 +23,9 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .llama import _FusedSlice
+from .llama import _FusedSlice, _HandOver, _rf_clear_hook
 from .qlinear import FusedQLinear, qlinear
-from .qtensor import act_quantize, layernorm_quantize
+from .qtensor import act_quantize, add_layernorm_quantize, layernorm_quantize
 
 
 class LayerNormQuant(nn.Module):
@@ -38,8 +42,12 @@ class LayerNormQuant(nn.Module):
             self.register_parameter("bias", None)
         self.eps = float(eps)
 
-    def forward(self, x: torch.Tensor):
-        return layernorm_quantize(x, self.weight, self.bias, self.eps)
+    def forward(self, x: torch.Tensor, residual: torch.Tensor | None = None):
+        """Without `residual`: the QTensor of LayerNorm(x).  With it: (QTensor of LayerNorm(residual + x), residual + x) from one kernel (K1al) — the bits of the
+        torch add followed by the call without `residual`."""
+        if residual is None:
+            return layernorm_quantize(x, self.weight, self.bias, self.eps)
+        return add_layernorm_quantize(x, residual, self.weight, self.bias, self.eps)
 
     def extra_repr(self):
         return f"{tuple(self.weight.shape)}, eps={self.eps}, bias={self.bias is not None} -> int8 per-token QTensor"
@@ -276,10 +284,310 @@ def fusable_activation(mlp: nn.Module):
     return name, kind
 
 
+# ---------------------------------------------------------------- the residual adds fused into the norms that follow them (opt-in)
+_H = "pq:norm-output"          # the place of the first norm's output in the recorded attention call
+_CONSTANTS = (type(None), bool, int, float, str)
+
+
+class ResidualPlan:
+    """What the probe of a block class's forward recorded (residual_flow_plan): the names of the four roles, the attention call to replay — for every positional
+    and keyword argument either _H, ("param", name of the block's own parameter handed on) or ("const", value) — whether the block's **kwargs go to the attention,
+    the block parameters the attention never saw (`withheld`: a call that sets one of them runs the original forward) and the stateless children (dropouts) that
+    the eval-mode probe found to be no-ops on the stream (a call in training mode runs the original forward)."""
+
+    def __init__(self, cls, n1, attn, n2, mlp, args, kwargs, var_kw, withheld, defaults, stateless):
+        self.cls, self.n1, self.attn, self.n2, self.mlp = cls, n1, attn, n2, mlp
+        self.args, self.kwargs, self.var_kw, self.withheld, self.defaults, self.stateless = tuple(args), dict(kwargs), var_kw, tuple(withheld), dict(defaults), tuple(stateless)
+        self.signature = inspect.signature(cls.forward)
+        ps = list(self.signature.parameters.values())
+        self.first = ps[1].name
+        self.var_kw_name = next((p.name for p in ps if p.kind == p.VAR_KEYWORD), None)
+
+
+class _ProbeBlock:
+    """Stand-in for `self` in a block class's own forward.  The two LayerNormQuant children and every child that holds parameters or buffers are recorders (the
+    roles are told apart by what they are called with); a child without state is an eval-mode copy of the real one; every other attribute is the real block's,
+    methods re-bound to the stand-in."""
+
+    def __init__(self, block, run):
+        self.__dict__["_block"], self.__dict__["_run"], self.__dict__["_kids"] = block, run, {}
+
+    def __getattr__(self, name):
+        v = getattr(self.__dict__["_block"], name)
+        if isinstance(v, nn.Module):
+            kids = self.__dict__["_kids"]
+            if name not in kids:
+                kids[name] = self.__dict__["_run"].child(name, v)
+            return kids[name]
+        if isinstance(v, types.MethodType) and v.__self__ is self.__dict__["_block"]:
+            return types.MethodType(v.__func__, self)
+        return v
+
+
+class _ProbeRun:
+    """One run of a block forward on exact small integers: the first norm called returns 2 t, the second t / 2 - 3; the child called with the first norm's output
+    is the attention and returns (h + 1, None), the child called with the second norm's output is the MLP and returns h * h.  Anything else is a refusal.
+    poison: one element of the attention's and one of the MLP's output are +Inf — a use of either that is invisible on finite values (times zero) gives a NaN."""
+
+    def __init__(self, norm_names, poison=False):
+        self.poison = poison
+        self.norm_names, self.norms, self.norm_out = set(norm_names), [], []          # norms: names in call order; norm_out: the tensors they returned
+        self.attn, self.mlp, self.attn_call, self.stateless = None, None, None, []
+
+    def child(self, name, v):
+        if name in self.norm_names:
+            def norm(t, _name=name):
+                if _name in self.norms or len(self.norms) >= 2 or not isinstance(t, torch.Tensor):
+                    raise _ProbeRefused(f"{_name} is called twice, or not with a tensor")
+                self.norms.append(_name)
+                out = t * 2.0 if len(self.norms) == 1 else t * 0.5 - 3.0
+                self.norm_out.append(out)
+                return out
+            return norm
+        if isinstance(v, (nn.ModuleList, nn.ModuleDict, nn.Sequential)):
+            raise _ProbeRefused(f"forward reads the container {name!r}")
+        if _stateless(v):
+            self.stateless.append(name)
+            return copy.deepcopy(v).eval()
+
+        def callee(*a, _name=name, **kw):
+            given = list(a) + list(kw.values())
+            if self.norm_out and any(g is self.norm_out[0] for g in given):
+                if self.attn is not None:
+                    raise _ProbeRefused("the first norm's output is used twice")
+                self.attn, self.attn_call = _name, (a, kw)
+                return self.poisoned(self.norm_out[0] + 1.0, 0), None
+            if len(self.norm_out) == 2 and len(a) == 1 and not kw and a[0] is self.norm_out[1]:
+                if self.mlp is not None:
+                    raise _ProbeRefused("the second norm's output is used twice")
+                self.mlp = _name
+                return self.poisoned(a[0] * a[0], -1)
+            raise _ProbeRefused(f"{_name} is called with something that is not a norm's output")
+        return callee
+
+    def poisoned(self, t, at):
+        if self.poison:
+            t = t.clone()
+            t.view(-1)[at] = float("inf")
+        return t
+
+
+def _probe_block_once(block, cls, norm_names, given, poison=False):
+    """cls.forward on a stand-in with the keyword arguments `given`; (run, the formula holds) or raises"""
+    run = _ProbeRun(norm_names, poison)
+    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
+    xin = x.clone()
+    with torch.no_grad(), torch.random.fork_rng(devices=[]):
+        out = cls.forward(_ProbeBlock(block, run), xin, **given)
+    r1 = x + run.poisoned(x * 2.0 + 1.0, 0)
+    n2 = r1 * 0.5 - 3.0
+    want = r1 + run.poisoned(n2 * n2, -1)
+    ok = (isinstance(out, torch.Tensor) and len(run.norms) == 2 and run.attn is not None and run.mlp is not None and out.shape == want.shape
+          and out.dtype == want.dtype and torch.equal(out, want) and torch.equal(xin, x))          # (a forward that writes into its input is refused)
+    return run, ok
+
+
+def residual_flow_plan(block: nn.Module, cls=None):
+    """A ResidualPlan iff `cls.forward` (default: the block's own class) IS the sequential pre-norm data flow on this block:
+
+        r1 = x + A(N1(x), ...)[0];   out = r1 + M(N2(r1))
+
+    with N1, N2 the block's two LayerNormQuant children, A and M two other children, each of the four called once, nothing else done to the stream (a child
+    without state — a dropout — may sit on it as long as the result still EQUALS the formula with that child in eval mode) and a tensor returned.  Probed, not
+    pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a tiny CPU tensor.  Every parameter of the forward is given
+    a sentinel object; where one arrives in the attention call — positionally or by keyword — is recorded, and so are the constants of that call.  A parameter
+    whose sentinel breaks the flow (GPT-2's encoder_hidden_states selects a cross-attention branch) is withheld: left at its default in the probe, and a call that
+    sets it runs the original forward.  A second run with every default, and a +Inf planted in the attention's and in the MLP's output, must show the same flow and
+    the same call.  None for everything else — a parallel residual
+    (GPT-NeoX, Falcon, Phi), a scaled residual, a post-norm, a third norm, an attention output used twice, a forward that writes into its input or that raises."""
+    cls = cls or type(block)
+    norm_names = [n for n, m in block.named_children() if isinstance(m, LayerNormQuant)]
+    if len(norm_names) != 2:
+        return None
+    try:
+        ps = list(inspect.signature(cls.forward).parameters.values())[2:]          # (self, hidden_states, ...)
+    except (TypeError, ValueError, AttributeError):
+        return None
+    named = [p for p in ps if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)]
+    if any(p.kind in (p.POSITIONAL_ONLY, p.VAR_POSITIONAL) for p in ps):
+        return None
+    var_kw = any(p.kind == p.VAR_KEYWORD for p in ps)
+    defaults = {p.name: p.default for p in named if p.default is not p.empty}
+    sentinels = {p.name: object() for p in named}
+    extra = object()
+
+    def attempt(withhold):
+        given = {n: s for n, s in sentinels.items() if n not in withhold}
+        if var_kw:
+            given["pq_probe_extra"] = extra
+        try:
+            run, ok = _probe_block_once(block, cls, norm_names, given)
+        except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
+            return None
+        return run if ok else None
+
+    # every parameter given; else one parameter withheld; else every parameter that has a default withheld
+    tries = [()] + [(n,) for n in defaults] + [tuple(defaults)]
+    run, withheld = None, ()
+    for withheld in tries:
+        run = attempt(withheld)
+        if run is not None:
+            break
+    if run is None:
+        return None
+    by_id = {id(s): n for n, s in sentinels.items()}
+
+    def entry(v):
+        if v is run.norm_out[0]:
+            return _H
+        if id(v) in by_id:
+            return ("param", by_id[id(v)])
+        if isinstance(v, _CONSTANTS):
+            return ("const", v)
+        raise _ProbeRefused("the attention is called with something the probe cannot replay")
+
+    a, kw = run.attn_call
+    kw = dict(kw)
+    forwards_extra = var_kw and kw.pop("pq_probe_extra", None) is extra
+    try:
+        args, kwargs = [entry(v) for v in a], {k: entry(v) for k, v in kw.items()}
+    except _ProbeRefused:
+        return None
+    if sum(e == _H for e in args) + sum(e == _H for e in kwargs.values()) != 1:
+        return None
+    seen = {e[1] for e in list(args) + list(kwargs.values()) if e != _H and e[0] == "param"}
+    withheld = tuple(n for n in sentinels if n not in seen)
+    if any(n not in defaults for n in withheld):          # a required parameter the attention never sees: nothing to fall back on
+        return None
+    # the same flow with every default (a parameter tested for truth must not change the stream): the recorded call must be the one made there too
+    try:
+        run2, ok2 = _probe_block_once(block, cls, norm_names, {n: s for n, s in sentinels.items() if n not in defaults}, poison=True)
+    except Exception:          # noqa: BLE001
+        return None
+    if not ok2 or (run2.norms, run2.attn, run2.mlp) != (run.norms, run.attn, run.mlp):
+        return None
+    a2, kw2 = run2.attn_call
+
+    def same(e, v):
+        if e == _H:
+            return v is run2.norm_out[0]
+        if e[0] == "param":
+            return v is (defaults[e[1]] if e[1] in defaults else sentinels[e[1]])
+        return type(v) is type(e[1]) and v == e[1]
+
+    if len(a2) != len(args) or set(kw2) != set(kwargs) or not all(same(e, v) for e, v in zip(args, a2)) or not all(same(kwargs[k], kw2[k]) for k in kwargs):
+        return None
+    return ResidualPlan(cls, run.norms[0], run.attn, run.norms[1], run.mlp, args, kwargs, forwards_extra, withheld, defaults, sorted(set(run.stateless) | set(run2.stateless)))
+
+
+class ResidualFusedBlock(nn.Module):
+    """A sequential pre-norm decoder block whose two residual adds run inside the LayerNorm + quantisation kernels that follow them (K1al, add_layernorm_quantize):
+
+        h          = the QTensor handed over for this very tensor, else N1(hidden)
+        attn_out   = A(...)[0], called the way the block's own forward calls it (ResidualPlan), with h in the norm output's place
+        hq, resid  = N2(attn_out, residual=hidden)                               # add + norm + quant, one launch
+        m          = M(hq)
+        last of the chain:  return resid + m                                     # a torch add
+        otherwise:          hq2, out = NEXT block's N1(m, residual=resid);  hand hq2 to the next block;  return out
+
+    What the block returns is the real summed tensor (the bits of the two torch adds: QSPEC A1), so hooks, output_hidden_states and the final norm see what they
+    saw.  fuse_layernorm_residual(model) makes a block one by giving the object a class that derives from this one AND from its original class: the object,
+    its children under their names (state_dict keys), its other attributes, its hooks and every isinstance check on it stay as they were.  The tensor the block was
+    called with is never written; the hand-over is consumed at the next block's entry and never served for another tensor or a tensor changed in place since.
+    Whatever the probe did not see — an argument the attention never receives set to something else than its default (GPT-2's encoder_hidden_states), training
+    mode with a dropout on the stream — runs the original class's forward for that call."""
+    _pq_residual_fused = True
+
+    def forward(self, *args, **kwargs):
+        plan = self._rfb_plan
+        bound = plan.signature.bind(self, *args, **kwargs)          # (a TypeError here is the one the original forward would raise)
+        bound.apply_defaults()
+        given = bound.arguments
+        extras = given.get(plan.var_kw_name, {}) if plan.var_kw_name else {}
+        hidden = given[plan.first]
+        if ((self.training and plan.stateless) or not isinstance(hidden, torch.Tensor) or (extras and not plan.var_kw)
+                or any(given[n] is not plan.defaults[n] for n in plan.withheld)):
+            self._rf_inbox.clear()
+            return plan.cls.forward(self, *args, **kwargs)
+        h = self._rf_inbox.take(hidden)
+        if h is None:
+            h = getattr(self, plan.n1)(hidden)
+        value = lambda e: h if e == _H else given[e[1]] if e[0] == "param" else e[1]          # noqa: E731
+        attn_out = getattr(self, plan.attn)(*(value(e) for e in plan.args), **{k: value(e) for k, e in plan.kwargs.items()}, **extras)[0]
+        hq, resid = getattr(self, plan.n2)(attn_out, residual=hidden)
+        m = getattr(self, plan.mlp)(hq)
+        nxt = self._rf_next[0]
+        if nxt is None:
+            return resid + m
+        hq2, out = getattr(nxt, nxt._rfb_plan.n1)(m, residual=resid)
+        nxt._rf_inbox.put(out, hq2)
+        return out
+
+    def __reduce_ex__(self, protocol):          # (the class is made at run time: a copy — deep or pickled — makes it again from the original class)
+        return _rebuild_fused_block, (self._rfb_plan.cls,), self.__dict__
+
+
+_RFB_CLASSES: dict = {}
+
+
+def _residual_fused_block_class(cls):
+    if cls not in _RFB_CLASSES:
+        _RFB_CLASSES[cls] = type("ResidualFused" + cls.__name__, (ResidualFusedBlock, cls), {"__doc__": ResidualFusedBlock.__doc__})
+    return _RFB_CLASSES[cls]
+
+
+def _rebuild_fused_block(cls):
+    fused = _residual_fused_block_class(cls)
+    return fused.__new__(fused)
+
+
+def fuse_layernorm_residual(model: nn.Module) -> int:
+    """Opt-in, after fuse_layernorm_layers (which it leaves exactly as it was: a separate entry, so nothing changes for a caller who does not ask): every block of a
+    ModuleList that has exactly two LayerNormQuant children and whose class's forward passes residual_flow_plan becomes a ResidualFusedBlock (in place).  A refused
+    block keeps the fusions it has and breaks the chain (its predecessor ends with a torch add); the model's final norm is not touched.  The module that owns the
+    ModuleList gets an always-called forward hook that drops every pending hand-over when its forward ends.  Returns the number of blocks changed by THIS call (a
+    second call finds nothing left to change); residual_fused_blocks(model) counts them over all calls.  Composes with fuse_llama_layers in any order."""
+    n = 0
+    for owner in list(model.modules()):
+        for _, stack in list(owner.named_children()):
+            if not isinstance(stack, nn.ModuleList):
+                continue
+            fresh = []
+            for block in stack:
+                if isinstance(block, ResidualFusedBlock) or getattr(type(block), "_pq_residual_fused", False):
+                    continue
+                plan = residual_flow_plan(block)
+                if plan is None:
+                    continue
+                block._rfb_plan = plan
+                block._rf_inbox, block._rf_next = _HandOver(), [None]
+                block.__class__ = _residual_fused_block_class(plan.cls)
+                fresh.append(block)
+            # (re)link the chain: a block hands over to its successor in the stack when that one is residual-fused too; anything else ends the chain with a torch add
+            for i, block in enumerate(stack):
+                if isinstance(block, ResidualFusedBlock):
+                    nxt = stack[i + 1] if i + 1 < len(stack) else None
+                    block._rf_next = [nxt if isinstance(nxt, ResidualFusedBlock) else None]          # (a list: the next block is registered once, in the stack)
+            if fresh:
+                if not hasattr(owner, "_rf_layers"):
+                    owner._rf_layers = []
+                    owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
+                owner._rf_layers.extend(fresh)
+                n += len(fresh)
+    return n
+
+
+def residual_fused_blocks(model: nn.Module) -> int:
+    """the number of ResidualFusedBlock modules in `model` (what fuse_layernorm_residual made, over all calls)"""
+    return sum(1 for m in model.modules() if isinstance(m, ResidualFusedBlock))
+
+
 def fuse_layernorm_layers(model: nn.Module, fuse_norms: bool = True, fuse_act: bool = True) -> int:
     """Apply the two fusions above to every block of `model` (in place) that passes the probes; returns the number of blocks changed.  A block is a module with at
     least one LayerNorm child; its MLP is looked for among its descendants.  Run after swap_linears: a block whose projections are still nn.Linear is left alone,
-    as is everything the probes refuse (fusable_norms, fusable_activation say what they require)."""
+    as is everything the probes refuse (fusable_norms, fusable_activation say what they require).
+
+    The residual adds of the blocks are a separate, opt-in step: fuse_layernorm_residual(model), afterwards."""
     changed = 0
     for block in reversed(list(model.modules())):          # inner blocks first: an MLP belongs to the innermost block around it
         if not any(isinstance(c, nn.LayerNorm) or isinstance(c, LayerNormQuant) for c in block.children()):

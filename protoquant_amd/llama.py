@@ -304,8 +304,9 @@ def _fuse_residual(model: nn.Module) -> int:
 
 
 def residual_fused_layers(model: nn.Module) -> int:
-    """the number of ResidualFusedLayer modules in `model` (what fuse_llama_layers(fuse_residual=True) made, over all calls)"""
-    return sum(1 for m in model.modules() if isinstance(m, ResidualFusedLayer))
+    """the number of residual-fused decoder layers in `model`: the ResidualFusedLayer modules fuse_llama_layers(fuse_residual=True) made and the ResidualFusedBlock
+    modules gptlike.fuse_layernorm_residual made, over all calls"""
+    return sum(1 for m in model.modules() if isinstance(m, ResidualFusedLayer) or getattr(type(m), "_pq_residual_fused", False))
 
 
 def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool = True, fuse_residual: bool = False) -> int:
@@ -314,7 +315,8 @@ def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
     fuse_residual=True (opt-in; the default leaves everything as it was): afterwards, every layer of a ModuleList whose two norms are RMSNormQuant and whose class's
     forward passes residual_flow_is_llama becomes a ResidualFusedLayer.  A refused layer keeps the fusions above and breaks the chain (its predecessor ends with a
     torch add).  The module that owns the ModuleList gets an always-called forward hook that drops every pending hand-over when its forward ends.  The return value
-    is unchanged; residual_fused_layers(model) counts the residual-fused layers.  (shard_llama_layers is not covered: its residual stream is replicated over the ranks
+    is unchanged; residual_fused_layers(model) counts the residual-fused layers.  A layer whose norms are LayerNorms (StarCoder2: this data flow, LayerNormQuant norms) is
+    ignored here: that switch is gptlike.fuse_layernorm_residual(model) (kernel K1al).  (shard_llama_layers is not covered: its residual stream is replicated over the ranks
     and its layers keep the torch adds.)"""
     n = 0
     for layer in model.modules():

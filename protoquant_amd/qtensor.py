@@ -322,6 +322,52 @@ def layernorm_quantize(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor
     return (qt, h.reshape(x.shape)) if return_h else qt
 
 
+def add_layernorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, eps: float = 1e-5, out: torch.Tensor | None = None,
+                           return_h: bool = False):
+    """summed = residual + x, then layernorm_quantize(summed, weight, bias, eps) — in ONE kernel (K1al): the new residual stream is stored once and normalised, reduced
+    and encoded from the registers that hold it.  Returns (QTensor, summed) or (QTensor, summed, h) with return_h=True; every one of them holds the bits of
+    layernorm_quantize(residual + x, weight, bias, eps, return_h=True) with the add done by torch (QSPEC A1: one binary32 add, one storage rounding, then L1-L6, Q1-Q6).
+    x and residual have the same shape, dtype and device; `bias` may be None.  `out` (optional, the same shape and dtype) receives the sum and may be x or residual
+    themselves; any other tensor that overlaps an input is refused.  `summed` has x's shape."""
+    L.require_gpu(x, "add_layernorm_quantize(x)")
+    L.require_gpu(residual, "add_layernorm_quantize(residual)")
+    if weight is None:
+        raise ValueError("add_layernorm_quantize: weight is None — a LayerNorm without affine parameters (elementwise_affine=False) is not supported")
+    L.require_gpu(weight, "add_layernorm_quantize(weight)")
+    if x.dim() < 1 or x.shape != residual.shape or x.dtype != residual.dtype or x.device != residual.device:
+        raise ValueError(f"add_layernorm_quantize: x {tuple(x.shape)} {x.dtype} {x.device} and residual {tuple(residual.shape)} {residual.dtype} {residual.device} must match")
+    if weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"add_layernorm_quantize: x {tuple(x.shape)} {x.dtype} needs a weight of shape ({x.shape[-1]},) and the same dtype/device, "
+                         f"got {tuple(weight.shape)} {weight.dtype}")
+    if bias is not None:
+        L.require_gpu(bias, "add_layernorm_quantize(bias)")
+        if bias.shape != weight.shape or bias.dtype != x.dtype or bias.device != x.device:
+            raise ValueError(f"add_layernorm_quantize: bias {tuple(bias.shape)} {bias.dtype} must match the weight {tuple(weight.shape)} {weight.dtype}")
+    if out is not None:
+        L.require_gpu(out, "add_layernorm_quantize(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"add_layernorm_quantize: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, "add_layernorm_quantize")
+    if rows == 0 or cols == 0:          # nothing to add: the empty sum through K1l (scales of empty rows are 1, QSPEC Q3)
+        res = layernorm_quantize(summed, weight, bias, eps, return_h)
+        return (res[0], summed, res[1]) if return_h else (res, summed)
+    w = weight.contiguous()
+    b = bias.contiguous() if bias is not None else None
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_add_layernorm_quant_rowwise(x2.data_ptr(), L.ld(x2), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2), w.data_ptr(),
+                                                       b.data_ptr() if b is not None else None, float(eps), code, rows, cols, q.data_ptr(), cols, scale.data_ptr(),
+                                                       h.data_ptr() if return_h else None, cols, L.stream_ptr(x)), "add_layernorm_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
+
+
 def act_quantize(x: torch.Tensor, kind: str, return_h: bool = False):
     """quantize(act(x), axis=-1) in ONE pass (kernel K1u) for the unary activation of a plain two-linear MLP: kind "relu" (torch.relu), "gelu_tanh" (gelu_new,
     gelu_pytorch_tanh) or "gelu_erf" (F.gelu's default).  x may be a column slice of a wider tensor.  Numerics: QSPEC U1-U4 then Q1-Q6 — relu holds torch's bits;
