@@ -264,8 +264,6 @@ __global__ __launch_bounds__(256) void act_quant_generic(const void* __restrict_
     for (int64_t c = threadIdx.x; c < cols; c += 256) qr[c] = (int8_t)code_of(Elem<DT>::to_f32(h_at(c)), s);
 }
 
-static inline bool act_aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int DT, int KIND, int TPR, bool WRITE_H>
 static void launch_act_vec(int vpt, const uint8_t* x, int64_t ldx_b, int64_t rows, int nvec, int8_t* q, int64_t ldq, float* scale, uint8_t* h, int64_t ldh_b,
                            hipStream_t st) {
@@ -299,8 +297,8 @@ template <int DT, int KIND>
 static void act_quant_dispatch_kind(const void* x, int64_t ldx, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh,
                                     hipStream_t st) {
     constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const bool vec_ok = cols > 0 && (cols % EPV == 0) && (ldx % EPV == 0) && act_aligned_to(x, 16) && (ldq % EPV == 0) && act_aligned_to(q, EPV) &&
-                        cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && act_aligned_to(h_out, 16)));
+    const bool vec_ok = cols > 0 && (cols % EPV == 0) && (ldx % EPV == 0) && aligned_to(x, 16) && (ldq % EPV == 0) && aligned_to(q, EPV) &&
+                        cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && aligned_to(h_out, 16)));
     if (!vec_ok) {
         act_quant_generic<DT, KIND><<<dim3((unsigned)rows), dim3(256), 0, st>>>(x, ldx, cols, q, ldq, scale, h_out, ldh);
         return;

@@ -1,9 +1,14 @@
-// addnorm_device.h — QSPEC A1 on one 16-byte vector, shared by the residual-fused producers K1a (addnorm_kernels.hip) and K1al (addlayernorm_kernels.hip).
+// addnorm_device.h — QSPEC A1 on one 16-byte vector, for the residual-fused producers K1a and K1al (rownorm_kernels.h).
 #pragma once
 #include "producer_device.h"
 
 namespace pq {
 
+// A1 for one element: one binary32 add (residual + x), then the storage rounding
+template <int DT>
+__device__ __forceinline__ typename Elem<DT>::store_t add_elem(typename Elem<DT>::store_t r, typename Elem<DT>::store_t x) {
+    return Elem<DT>::from_f32(Elem<DT>::to_f32(r) + Elem<DT>::to_f32(x));
+}
 // A1 on one 16-byte vector: one binary32 add per element (residual + x), then the storage rounding
 template <int DT>
 __device__ __forceinline__ v4u add_vec(const v4u& xv, const v4u& rv) {

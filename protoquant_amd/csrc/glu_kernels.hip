@@ -279,8 +279,6 @@ void launch_glu_short_check(int dtype, int kind, float limit, float alpha, unsig
     }
 }
 
-static inline bool glu_aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int DT, int KIND, int TPR, bool WRITE_H>
 static void launch_glu_vec(int vpt, const uint8_t* g, int64_t ldg_b, const uint8_t* u, int64_t ldu_b, int64_t rows, int nvec, float L, float alpha, uint32_t gb,
                            int8_t* q, int64_t ldq, float* scale, uint8_t* h, int64_t ldh_b, hipStream_t st) {
@@ -316,8 +314,8 @@ template <int DT, int KIND>
 static void glu_quant_dispatch_kind(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, float L, float alpha, uint32_t gb,
                                     int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st) {
     constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const bool vec_ok = (cols % EPV == 0) && (ldg % EPV == 0) && (ldu % EPV == 0) && glu_aligned_to(g, 16) && glu_aligned_to(u, 16) && (ldq % EPV == 0) &&
-                        glu_aligned_to(q, EPV) && cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && glu_aligned_to(h_out, 16)));
+    const bool vec_ok = (cols % EPV == 0) && (ldg % EPV == 0) && (ldu % EPV == 0) && aligned_to(g, 16) && aligned_to(u, 16) && (ldq % EPV == 0) &&
+                        aligned_to(q, EPV) && cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && aligned_to(h_out, 16)));
     if (!vec_ok) {
         glu_quant_generic<DT, KIND><<<dim3((unsigned)rows), dim3(256), 0, st>>>(g, ldg, u, ldu, cols, L, alpha, q, ldq, scale, h_out, ldh);
         return;

@@ -1,6 +1,5 @@
-// layernorm_device.h — the device helpers of the LayerNorm-family producers (QSPEC L1-L6), shared by K1l (layernorm_kernels.hip) and K1al
-// (addlayernorm_kernels.hip): L2 / L3 / L5 on one 16-byte vector, the wave-level sum of the one-wave-per-row layout and the pin that keeps the loads of the weight
-// and bias rows behind the first reduction exist once.  Everything is __forceinline__: each kernel file keeps its own templates in its own object.
+// layernorm_device.h — the device helpers of the LayerNorm-family producers (QSPEC L1-L6), for K1l and K1al
+// (rownorm_kernels.h): L2 / L3 / L5 on one 16-byte vector.  Everything is __forceinline__.
 #pragma once
 #include "producer_device.h"
 
@@ -57,25 +56,6 @@ __device__ __forceinline__ v4u ln_h_vec(const v4u& xv, const v4u& wv, const v4u&
         }
     }
     return out;
-}
-
-// An empty statement that takes every vector of the row as an operand and clobbers memory: the loads written after it (the weight and bias rows) are issued after
-// the first pass over the row has started, not hoisted above the loads of x (addnorm_kernels.hip: pin_before_loads)
-template <int VPT>
-__device__ __forceinline__ void ln_pin_before_loads(v4u (&xv)[VPT]) {
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) asm volatile("" : "+v"(xv[i]) : : "memory");
-}
-
-// Short rows: one WAVE per row, four rows per block and no block barrier, as rmsnorm_quant_wave — physical lane l holds the virtual lanes l, l + 64, l + 128,
-// l + 192 of the specification, one accumulator per group, the xor butterfly on each, the four sums left to right: the same float operations in the same order.
-__device__ __forceinline__ float ln_wave_sum(float (&acc)[4]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi) acc[gi] = acc[gi] + __shfl_xor(acc[gi], off, 64);
-    }
-    return ((acc[0] + acc[1]) + acc[2]) + acc[3];
 }
 
 }  // namespace pq

@@ -64,6 +64,8 @@ struct Options {
 // the snapshot pinned by the C-ABI call in progress on this thread (outside a call: the live one)
 const Options& opt();
 
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // a: a power of two
+
 // ---------------------------------------------------------------- write-through global stores
 // Output streams (codes, dequantised tiles, y) are stored with the sc1 cache policy: the line is written through to the memory side
 // and dropped from the XCD's L2 instead of staying there dirty.  A kernel that leaves B dirty bytes in L2 pays ~B / 6 TB/s at its

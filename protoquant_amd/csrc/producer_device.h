@@ -281,15 +281,35 @@ __device__ __forceinline__ void reduce_and_encode(const v4u (&hv)[VPT], uint32_t
 }
 
 // ------------------------------------------------------------------------------------------------
-// QSPEC N1-N5, shared by K1n (producer_kernels.hip) and K1a (addnorm_kernels.hip): ONE copy of the pinned summation order.  The reduction order N1-N3 is the
-// 256-thread layout: vector v on lane v mod 256, xor butterfly per 64 lanes, the four wave sums left to right.
-__device__ __forceinline__ float rms_block_sum(float acc) {
+// QSPEC N1-N5 for the norm family (rownorm_kernels.h): ONE copy of the pinned summation order.  The reduction order N1-N3 is the 256-thread layout: vector v on
+// lane v mod 256, xor butterfly per 64 lanes, the four wave sums left to right.
+// The butterfly on N independent sums at once, step by step: every lane ends with the sums over its wave.
+template <int N>
+__device__ __forceinline__ void wave_sums(float (&acc)[N]) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int gi = 0; gi < N; ++gi) acc[gi] = acc[gi] + __shfl_xor(acc[gi], off, 64);
+    }
+}
+// one block per row: this lane's sum -> the row's.  The wave sums meet in ONE array per kernel: a barrier goes between two calls.
+__device__ __forceinline__ float rms_block_sum(float acc) {
+    float a[1] = {acc};
+    wave_sums(a);
     __shared__ float wsum[4];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a[0];
     __syncthreads();
     return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// the row's sum in either layout of rownorm_kernels.h.  One wave per row: the wave holds all four 64-lane groups of the specification, one accumulator each.
+template <int TPR>
+__device__ __forceinline__ float row_sum(float (&acc)[TPR == 64 ? 4 : 1]) {
+    if constexpr (TPR == 64) {
+        wave_sums(acc);
+        return ((acc[0] + acc[1]) + acc[2]) + acc[3];
+    } else {
+        return rms_block_sum(acc[0]);
+    }
 }
 __device__ __forceinline__ float rms_rs(float ss, int cols, float eps) {
     const float var = ss / (float)cols;

@@ -1,13 +1,13 @@
 // producer_kernels.hip — K1 fused into the op that produces the activation:
 //   silu(g) * u           ->  per-token int8 codes + row scales   (K1s: the `down` input of a gated MLP)
-//   RMSNorm(x; weight)    ->  per-token int8 codes + row scales   (K1n: the q/k/v and gate/up input of a decoder layer)
+//   RMSNorm(x; weight)    ->  per-token int8 codes + row scales   (K1n: the q/k/v and gate/up input of a decoder layer; kernels in rownorm_kernels.h)
 // without the bf16 activation ever going to HBM.
 // Same skeleton as K1 (quant_kernels.hip): TPR threads own a row, the row of h lives in registers between the amax
 // reduction and the encode; here it is COMPUTED from one 16-byte vector of g and one of u per slot instead of loaded.
 // Arithmetic follows QSPEC S1-S6: a specified exponential (Cody-Waite + degree-7 Horner with fma),
 // IEEE division, storage-dtype rounding after silu and after the product — bit-identical to oracle/qspec_oracle.c.
 // Algorithmic traffic: read 2 x elem bytes, write 1 B/elem + 4 B/row (+ elem bytes when h is also requested).
-#include "producer_device.h"
+#include "rownorm_kernels.h"
 
 namespace pq {
 
@@ -114,140 +114,6 @@ __global__ __launch_bounds__(256) void silu_mul_quant_generic(const void* __rest
     for (int64_t c = threadIdx.x; c < cols; c += 256) qr[c] = (int8_t)code_of(Elem<DT>::to_f32(h_at(c)), s);
 }
 
-// ------------------------------------------------------------------------------------------------
-// K1n: RMSNorm fused into the per-token quantisation (QSPEC N1-N6).  One row per 256-thread block (the reduction order N1-N3
-// IS this layout: vector v on lane v mod 256, xor butterfly per 64 lanes, the four wave sums left to right).  Reads x once
-// (2 B/elem) and the weight vector from L2, writes 1 B/elem + 4 B/row: the normalised bf16 activation never goes to HBM.
-// (rms_block_sum, rms_rs, rms_h, rms_h_vec: producer_device.h — shared with K1a, addnorm_kernels.hip)
-template <int DT, int VPT, bool WRITE_H>
-__global__ __launch_bounds__(256) void rmsnorm_quant_vec(const uint8_t* __restrict__ x, int64_t ldx_bytes, const uint8_t* __restrict__ wgt,
-                                                         float eps, int cols, int nvec, int8_t* __restrict__ q, int64_t ldq,
-                                                         float* __restrict__ scale, uint8_t* __restrict__ h_out, int64_t ldh_bytes) {
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const int t = threadIdx.x;
-    const int64_t row = blockIdx.x;
-    const uint8_t* xr = x + row * ldx_bytes;
-    v4u xv[VPT], wv[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = i * 256 + t;
-        const int64_t off = (int64_t)(idx < nvec ? idx : nvec - 1) * 16;
-        xv[i] = *reinterpret_cast<const v4u*>(xr + off);
-        wv[i] = *reinterpret_cast<const v4u*>(wgt + off);
-    }
-    float acc = 0.0f;                       // N2: this lane's vectors in increasing v, elements in order
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        if (i * 256 + t >= nvec) xv[i] = v4u{0u, 0u, 0u, 0u};      // past the row: fma(0, 0, acc) = acc
-        float f[EPV];
-        Unpack<DT, EPV>::run(xv[i], f);
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) acc = __builtin_fmaf(f[j], f[j], acc);
-    }
-    const float rs = rms_rs(rms_block_sum(acc), cols, eps);        // N3, N4
-    v4u hv[VPT];
-    uint32_t ab = 0;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        hv[i] = rms_h_vec<DT>(xv[i], wv[i], rs);
-        ab = vec_amax_bits<DT>(hv[i], ab);
-        if constexpr (WRITE_H) {
-            const int idx = i * 256 + t;
-            if (idx < nvec) store_wt_b128(h_out + row * ldh_bytes + (int64_t)idx * 16, hv[i]);
-        }
-    }
-    reduce_and_encode<DT, VPT, 256>(hv, ab, t, nvec, true, row, q, ldq, scale);
-}
-
-// Short rows (at most 512 vectors, e.g. a 4096-wide bf16 hidden state): one WAVE per row, four rows per block and no block
-// barrier, like K1.  The wave plays all four 64-lane groups of the specification: physical lane l holds virtual lanes
-// l, l+64, l+128, l+192 (vector v = i*64 + l belongs to virtual lane v mod 256 = (i mod 4)*64 + l), keeps one accumulator
-// per group, runs the xor butterfly on each and adds the four sums left to right — the same float operations in the same
-// order as the 256-thread layout, so the same bits.
-template <int DT, int VPT, bool WRITE_H>
-__global__ __launch_bounds__(256) void rmsnorm_quant_wave(const uint8_t* __restrict__ x, int64_t ldx_bytes, const uint8_t* __restrict__ wgt,
-                                                          float eps, int cols, int nvec, int64_t rows, int8_t* __restrict__ q, int64_t ldq,
-                                                          float* __restrict__ scale, uint8_t* __restrict__ h_out, int64_t ldh_bytes) {
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const int t = threadIdx.x & 63;
-    int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const bool active = row < rows;
-    row = active ? row : rows - 1;
-    const uint8_t* xr = x + row * ldx_bytes;
-    v4u xv[VPT], wv[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = i * 64 + t;
-        const int64_t off = (int64_t)(idx < nvec ? idx : nvec - 1) * 16;
-        xv[i] = *reinterpret_cast<const v4u*>(xr + off);
-        wv[i] = *reinterpret_cast<const v4u*>(wgt + off);
-    }
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        if (i * 64 + t >= nvec) xv[i] = v4u{0u, 0u, 0u, 0u};
-        float f[EPV];
-        Unpack<DT, EPV>::run(xv[i], f);
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) acc[i & 3] = __builtin_fmaf(f[j], f[j], acc[i & 3]);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi) acc[gi] = acc[gi] + __shfl_xor(acc[gi], off, 64);
-    }
-    const float rs = rms_rs(((acc[0] + acc[1]) + acc[2]) + acc[3], cols, eps);
-    v4u hv[VPT];
-    uint32_t ab = 0;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        hv[i] = rms_h_vec<DT>(xv[i], wv[i], rs);
-        ab = vec_amax_bits<DT>(hv[i], ab);
-        if constexpr (WRITE_H) {
-            const int idx = i * 64 + t;
-            if (active && idx < nvec) store_wt_b128(h_out + row * ldh_bytes + (int64_t)idx * 16, hv[i]);
-        }
-    }
-    reduce_and_encode<DT, VPT, 64>(hv, ab, t, nvec, active, row, q, ldq, scale);
-}
-
-// generic path (ragged widths, unaligned pointers): the same lane layout walked element by element.
-template <int DT>
-__global__ __launch_bounds__(256) void rmsnorm_quant_generic(const void* __restrict__ x, int64_t ldx, const void* __restrict__ wgt, float eps,
-                                                             int64_t cols, int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale,
-                                                             void* __restrict__ h_out, int64_t ldh) {
-    using S = typename Elem<DT>::store_t;
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const int64_t row = blockIdx.x;
-    const S* xr = reinterpret_cast<const S*>(x) + row * ldx;
-    const S* wr = reinterpret_cast<const S*>(wgt);
-    const int64_t nvec = (cols + EPV - 1) / EPV;
-    float acc = 0.0f;
-    for (int64_t v = threadIdx.x; v < nvec; v += 256)
-        for (int e = 0; e < EPV && v * EPV + e < cols; ++e) {
-            const float f = Elem<DT>::to_f32(xr[v * EPV + e]);
-            acc = __builtin_fmaf(f, f, acc);
-        }
-    const float rs = rms_rs(rms_block_sum(acc), (int)cols, eps);
-    auto h_at = [&](int64_t c) -> S { return Elem<DT>::from_f32(rms_h<DT>(Elem<DT>::to_f32(xr[c]), Elem<DT>::to_f32(wr[c]), rs)); };
-    float amax = 0.0f;
-    for (int64_t c = threadIdx.x; c < cols; c += 256) {
-        const S h = h_at(c);
-        if (h_out) reinterpret_cast<S*>(h_out)[row * ldh + c] = h;
-        amax = amax_step(amax, Elem<DT>::to_f32(h));
-    }
-    amax = wave_max(amax);
-    __shared__ float part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = amax;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 4; ++w) amax = amax_merge(amax, part[w]);
-    const float s = scale_of(amax);
-    if (threadIdx.x == 0) scale[row] = s;
-    int8_t* qr = q + row * ldq;
-    for (int64_t c = threadIdx.x; c < cols; c += 256) qr[c] = (int8_t)code_of(Elem<DT>::to_f32(h_at(c)), s);
-}
-
 // dev/test kernel: every 16-bit pattern g of the fast-division domain (0 < |g| <= 86) through the three division forms, u = 1 (so h is the
 // stored silu(g)).  out[0] += patterns in the domain, out[1] += patterns whose SHORT result differs from the two-correction form,
 // out[2] += patterns whose two-correction form differs from true division.
@@ -268,13 +134,6 @@ void launch_silu_short_check(int dtype, unsigned long long* out, hipStream_t st)
     if (dtype == PQ_BF16) silu_short_check<PQ_BF16><<<dim3(256), dim3(256), 0, st>>>(out);
     else silu_short_check<PQ_FP16><<<dim3(256), dim3(256), 0, st>>>(out);
 }
-
-static inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// widest row (in 16-byte vectors) of the wave-per-row RMSNorm layout (pq_set_option("PQ_RMS_WAVE_MAX"), 0..512).  Round 1 used it up to
-// 512 vectors (a 4096-wide bf16 hidden state): 118 VGPRs, 4 waves per SIMD.  Measured in round 2 (profiles/r02_k1n_layout.txt): at 512
-// vectors the 256-thread block per row (2 vectors per thread, ~44 VGPRs) is 10 % faster at 4096 rows (15.7 -> 14.2 us) and equal at 16384;
-// at 256 vectors the wave layout wins (8.7 vs 9.6 us).  Same bits either way (QSPEC N1-N3 pins the order of the sum).
 
 template <int DT, int TPR, bool WRITE_H, int MODE = 0, bool IDENT = false>
 static void launch_silu_mul_vec(int vpt, const uint8_t* g, int64_t ldg_b, const uint8_t* u, int64_t ldu_b, int64_t rows, int nvec,
@@ -357,51 +216,19 @@ void silu_mul_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t 
     }
 }
 
+// K1n: the kernels and the layout decision are the norm family's (rownorm_kernels.h), ADD = false
 template <int DT>
-void rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq,
-                            float* scale, void* h_out, int64_t ldh, hipStream_t st) {
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const bool vec_ok = (cols % EPV == 0) && (ldx % EPV == 0) && aligned_to(x, 16) && aligned_to(wgt, 16) && (ldq % EPV == 0) &&
-                        aligned_to(q, EPV) && cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && aligned_to(h_out, 16)));
-    const dim3 grid((unsigned)rows), block(256);
-    if (!vec_ok) {
-        rmsnorm_quant_generic<DT><<<grid, block, 0, st>>>(x, ldx, wgt, eps, cols, q, ldq, scale, h_out, ldh);
-        return;
-    }
-    const int nvec = (int)(cols / EPV);
-    const uint8_t* xb = reinterpret_cast<const uint8_t*>(x);
-    const uint8_t* wb = reinterpret_cast<const uint8_t*>(wgt);
-    uint8_t* hb = reinterpret_cast<uint8_t*>(h_out);
+void rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
+                            void* h_out, int64_t ldh, hipStream_t st) {
     const int64_t kb = Elem<DT>::kBytes;
-    if (nvec <= opt().rms_wave_max) {         // one wave per row (rmsnorm_quant_wave): VPT in {4, 8} keeps i & 3 meaningful
-        const dim3 wgrid((unsigned)((rows + 3) / 4));
-#define PQ_RMSW_LAUNCH(V)                                                                                                                 \
-    do {                                                                                                                              \
-        if (h_out) rmsnorm_quant_wave<DT, V, true><<<wgrid, block, 0, st>>>(xb, ldx * kb, wb, eps, (int)cols, nvec, rows, q, ldq, scale, hb, ldh * kb); \
-        else rmsnorm_quant_wave<DT, V, false><<<wgrid, block, 0, st>>>(xb, ldx * kb, wb, eps, (int)cols, nvec, rows, q, ldq, scale, hb, 0);              \
-    } while (0)
-        if (nvec <= 64) PQ_RMSW_LAUNCH(1);
-        else if (nvec <= 128) PQ_RMSW_LAUNCH(2);
-        else if (nvec <= 256) PQ_RMSW_LAUNCH(4);
-        else PQ_RMSW_LAUNCH(8);
-#undef PQ_RMSW_LAUNCH
-        return;
-    }
-    int vpt = 1;
-    while (vpt * 256 < nvec) vpt <<= 1;
-#define PQ_RMS_LAUNCH(V)                                                                                                              \
-    do {                                                                                                                              \
-        if (h_out) rmsnorm_quant_vec<DT, V, true><<<grid, block, 0, st>>>(xb, ldx * kb, wb, eps, (int)cols, nvec, q, ldq, scale, hb, ldh * kb); \
-        else rmsnorm_quant_vec<DT, V, false><<<grid, block, 0, st>>>(xb, ldx * kb, wb, eps, (int)cols, nvec, q, ldq, scale, hb, 0);              \
-    } while (0)
-    switch (vpt) {
-        case 1: PQ_RMS_LAUNCH(1); break;
-        case 2: PQ_RMS_LAUNCH(2); break;
-        case 4: PQ_RMS_LAUNCH(4); break;
-        case 8: PQ_RMS_LAUNCH(8); break;
-        default: PQ_RMS_LAUNCH(16); break;
-    }
-#undef PQ_RMS_LAUNCH
+    rownorm_dispatch<DT>(
+        {{x, ldx}, {wgt, 0}}, rows, cols, q, ldq, h_out, ldh,
+        [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
+            rmsnorm_quant_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(write_h)::value, false><<<grid, dim3(256), 0, st>>>(
+                reinterpret_cast<const uint8_t*>(x), ldx * kb, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(wgt), eps, (int)cols, nvec, rows, q, ldq,
+                scale, reinterpret_cast<uint8_t*>(h_out), ldh * kb);
+        },
+        [&](dim3 grid) { rmsnorm_quant_generic<DT, false><<<grid, dim3(256), 0, st>>>(x, ldx, nullptr, 0, nullptr, 0, wgt, eps, cols, q, ldq, scale, h_out, ldh); });
 }
 
 template void rmsnorm_quant_dispatch<PQ_BF16>(const void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);

@@ -434,8 +434,6 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int8_t* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from pq_api.hip)
-static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int DT, int TPR>
 static void launch_rowwise_vec(int vpt, const void* x, int64_t rows, int nvec, int64_t ldx_bytes, int8_t* q,
                                int64_t ldq, float* scale, hipStream_t st) {
@@ -488,8 +486,8 @@ void quant_rowwise_dispatch(const void* x, int64_t rows, int64_t cols, int64_t l
                             float* scale, hipStream_t st) {
     constexpr int EPV = 16 / Elem<DT>::kBytes;
     // (cols == 0 goes to the generic kernel: it touches no element and writes scale = 1)
-    const bool vec_ok = cols > 0 && (cols % EPV == 0) && (ldx % EPV == 0) && aligned(x, 16) && (ldq % EPV == 0) &&
-                        aligned(q, EPV) && cols / EPV <= 256 * 32;
+    const bool vec_ok = cols > 0 && (cols % EPV == 0) && (ldx % EPV == 0) && aligned_to(x, 16) && (ldq % EPV == 0) &&
+                        aligned_to(q, EPV) && cols / EPV <= 256 * 32;
     if (vec_ok) {
         const int nvec = (int)(cols / EPV);
         auto pow2 = [](int v) { int p = 1; while (p < v) p <<= 1; return p; };
@@ -511,7 +509,7 @@ template <int DT>
 hipError_t quant_colwise_dispatch(const void* x, int64_t rows, int64_t cols, int64_t ldx, int8_t* q, int64_t ldq,
                                   float* scale, hipStream_t st) {
     constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const bool vec_ok = (cols % EPV == 0) && (ldx % EPV == 0) && aligned(x, 16) && (ldq % EPV == 0) && aligned(q, EPV);
+    const bool vec_ok = (cols % EPV == 0) && (ldx % EPV == 0) && aligned_to(x, 16) && (ldq % EPV == 0) && aligned_to(q, EPV);
     const int64_t ncolv = vec_ok ? cols / EPV : cols;
     // rows per block: enough blocks to keep ~48 KiB per CU in flight (6 TB/s x ~2 us of latency over 256 CUs) without drowning the amax pass in per-block LDS
     // merges and atomics: ~2 blocks per CU for the amax pass (16 KiB of raw vectors in flight per block), ~4 per CU for the encode pass (8 rows deep, no atomics);
@@ -553,8 +551,8 @@ template <int ODT>
 void dequant_dispatch(const int8_t* q, int64_t ldq, const float* scale, int axis, int64_t rows, int64_t cols,
                       void* out, int64_t ldo, hipStream_t st) {
     constexpr int EPT = 16 / Elem<ODT>::kBytes;
-    const bool vec_ok = (cols % EPT == 0) && (ldq % EPT == 0) && aligned(q, EPT) && aligned(out, 16) &&
-                        ((ldo * Elem<ODT>::kBytes) % 16 == 0) && (axis != 0 || aligned(scale, 16));
+    const bool vec_ok = (cols % EPT == 0) && (ldq % EPT == 0) && aligned_to(q, EPT) && aligned_to(out, 16) &&
+                        ((ldo * Elem<ODT>::kBytes) % 16 == 0) && (axis != 0 || aligned_to(scale, 16));
     const int64_t ncolv = vec_ok ? cols / EPT : cols;
     const dim3 grid((unsigned)((rows + 3) / 4), (unsigned)((ncolv + 63) / 64)), block(256);
     if (vec_ok) dequant_kernel<ODT, true><<<grid, block, 0, st>>>(q, ldq, scale, axis, rows, ncolv, out, ldo);

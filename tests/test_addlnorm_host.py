@@ -170,10 +170,10 @@ def test_code_object_has_every_layout_and_no_scratch():
     for dt in range(3):
         for wh in "01":
             for v in (1, 2, 4, 8):          # one wave per row: 1, 2, 4, 8 vectors per lane
-                assert len([n for n in k if re.search(r"add_layernorm_quant_waveILi%dELi%dELb%sE" % (dt, v, wh), n)]) == 1, (dt, v, wh)
+                assert len([n for n in k if re.search(r"\d+layernorm_quant_rowsILi%dELi%dELi64ELb%sELb1EE" % (dt, v, wh), n)]) == 1, (dt, v, wh)
             for v in (1, 2, 4, 8, 16):      # 256 threads per row: 1 .. 16 vectors per thread
-                assert len([n for n in k if re.search(r"add_layernorm_quant_vecILi%dELi%dELb%sE" % (dt, v, wh), n)]) == 1, (dt, v, wh)
-        assert len([n for n in k if re.search(r"add_layernorm_quant_genericILi%dE" % dt, n)]) == 1, dt
+                assert len([n for n in k if re.search(r"\d+layernorm_quant_rowsILi%dELi%dELi256ELb%sELb1EE" % (dt, v, wh), n)]) == 1, (dt, v, wh)
+        assert len([n for n in k if re.search(r"\d+layernorm_quant_genericILi%dELb1EE" % dt, n)]) == 1, dt
     assert len(k) == 3 * (8 + 10 + 1)
     for n, v in k.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (n, v)
@@ -185,4 +185,4 @@ def test_the_new_kernels_are_in_an_object_of_their_own():
     """the pre-existing producer objects keep their kernels: nothing of K1al is instantiated in layernorm_kernels.o or addnorm_kernels.o"""
     for obj in ("layernorm_kernels", "addnorm_kernels"):
         k, _ = _kernels_of(obj)
-        assert len(k) == 57 and not [n for n in k if "add_layernorm" in n], obj
+        assert len(k) == 57 and not [n for n in k if re.search(r"\d+layernorm_quant_(rowsILi\d+ELi\d+ELi\d+ELb[01]|genericILi\d+)ELb1EE", n)], obj

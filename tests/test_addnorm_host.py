@@ -142,7 +142,8 @@ def test_spec_is_the_add_then_the_oracle():
 
 
 def test_code_object_has_every_layout_and_no_scratch():
-    """as `make spillcheck` reads the GEMM objects: add_rmsnorm_quant_wave / _vec / _generic for all three dtypes, with and without h_out, none with scratch or spills"""
+    """as `make spillcheck` reads the GEMM objects: rmsnorm_quant_rows<.., 64 | 256, .., ADD = true> / rmsnorm_quant_generic<.., true> for all three dtypes, with and
+    without h_out, none with scratch or spills"""
     build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
     obj = os.path.join(build, "addnorm_kernels.o")
     llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
@@ -162,9 +163,9 @@ def test_code_object_has_every_layout_and_no_scratch():
             kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
     for dt in range(3):
         # wave: 1, 2, 4, 8 vectors per lane; vec: 1, 2, 4, 8, 16 per thread; each with and without h_out; one generic kernel
-        assert len([k for k in kernels if re.search(r"add_rmsnorm_quant_waveILi%dE" % dt, k)]) == 4 * 2, dt
-        assert len([k for k in kernels if re.search(r"add_rmsnorm_quant_vecILi%dE" % dt, k)]) == 5 * 2, dt
-        assert len([k for k in kernels if re.search(r"add_rmsnorm_quant_genericILi%dE" % dt, k)]) == 1, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb1EE" % dt, k)]) == 4 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb1EE" % dt, k)]) == 5 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_genericILi%dELb1EE" % dt, k)]) == 1, dt
     assert len(kernels) == 3 * (8 + 10 + 1)
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)

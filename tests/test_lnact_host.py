@@ -153,9 +153,9 @@ FORBIDDEN = re.compile(r"\bs_\w*(store|atomic|dcache)\w*|\bscratch_", re.I)     
 def test_code_objects_have_every_layout_and_no_scratch():
     kl, dl = _kernels_of("layernorm_kernels")
     for dt in range(3):
-        assert len([k for k in kl if re.search(r"layernorm_quant_waveILi%dE" % dt, k)]) == 4 * 2, dt          # 1, 2, 4, 8 vectors per lane, with / without h_out
-        assert len([k for k in kl if re.search(r"layernorm_quant_vecILi%dE" % dt, k)]) == 5 * 2, dt           # 1 .. 16 vectors per thread
-        assert len([k for k in kl if re.search(r"layernorm_quant_genericILi%dE" % dt, k)]) == 1, dt
+        assert len([k for k in kl if re.search(r"\d+layernorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb0EE" % dt, k)]) == 4 * 2, dt          # 1, 2, 4, 8 vectors per lane, with / without h_out
+        assert len([k for k in kl if re.search(r"\d+layernorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb0EE" % dt, k)]) == 5 * 2, dt           # 1 .. 16 vectors per thread
+        assert len([k for k in kl if re.search(r"\d+layernorm_quant_genericILi%dELb0EE" % dt, k)]) == 1, dt
     assert len(kl) == 3 * (8 + 10 + 1)
     ka, da = _kernels_of("act_kernels")
     for dt in range(3):
