@@ -9,6 +9,7 @@
 // use, the row of h lives in registers between the amax reduction and the encode.  The device helpers are CALLED from producer_device.h; the kernels here are
 // templates of their own in an object file of their own.
 #include "producer_device.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -6,6 +6,7 @@
 // The kernels and the layout decision are the norm family's (rownorm_kernels.h), ADD = true; they are instantiated here, in an object file of their own, so the
 // register allocation of K1l / K1a does not depend on this file.
 #include "rownorm_kernels.h"
+#include "pq_launch.h"
 
 namespace pq {
 

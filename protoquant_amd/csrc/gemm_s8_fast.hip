@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "gemm_tile_common.h"
+#include "pq_launch.h"
 #include "kloop_p3_asm.inc"   // generated: tools/gen_kloop_asm.py
 
 namespace pq {

@@ -6,6 +6,7 @@
 // lane's 4 accumulator registers are 4 consecutive n of one output row m: the epilogue stores them as
 // one contiguous piece of y[m, :].
 #include "gemm_epilogue.h"
+#include "pq_launch.h"
 
 namespace pq {
 

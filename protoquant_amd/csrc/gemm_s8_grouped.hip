@@ -18,6 +18,7 @@
 //   * same MFMA, same integer sums, same epilogue arithmetic as every other variant: bit-identical to pq_qlinear_s8 run once per expert on that expert's row slice.
 // Untrusted device data: offsets are clamped into [0, M_total] and the row index into [0, x_rows): wrong contents give wrong results, never an access outside the operands.
 #include "gemm_tile_common.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "gemm_epilogue.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -8,7 +8,7 @@
 // 128 x 128: half the chip at that rate.
 // Splitting K over workgroups (the fused hand-over of the big tile) costs ~3 - 4 us of store -> ticket -> load latency, as much as it saves on a 10-us launch.  So this kernel
 // goes the other way: smaller tiles on EVERY CU, with the loader / consumer structure of the ring tile, rings of 3 slots x 2 K-tiles x 24 KiB / 4 x 2 x 16 KiB (one barrier per
-// slot) and a K walk rotated between the workgroups that share a weight panel (below).  The dispatcher (pq_api.hip: pick_variant) chooses between the three ring tiles by
+// slot) and a K walk rotated between the workgroups that share a weight panel (below).  The dispatcher (pq_plan.hip: pick_variant) chooses between the three ring tiles by
 // rounds of 256 CUs x the measured time of one tile.
 //   * 8 waves: waves 0-3 consume (2 x 2 over the tile: wave tile (TN/2) n x (TM/2) m, fragments of the next K-tile read in the shadows of the
 //     current one's MFMAs, double-buffered in registers), waves 4-7 issue the LDS-DMA pieces (8 rows x 128 B each) of tile kt + NB and do the
@@ -18,6 +18,7 @@
 //   * epilogue: gemm_epilogue.h (QSPEC E1-E4 in registers, wave-private transpose through a free ring slot, write-through 16-byte stores);
 //     ragged edges through guarded direct stores.  Same MFMA, same integer sums, same epilogue arithmetic as every other variant: bit-identical.
 #include "gemm_tile_common.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "producer_device.h"
+#include "pq_launch.h"
 
 namespace pq {
 

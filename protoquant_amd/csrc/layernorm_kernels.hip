@@ -5,6 +5,7 @@
 // followed by K1); the weight and bias rows come from cache.
 // The kernels and the layout decision are the norm family's (rownorm_kernels.h), ADD = false; they are instantiated here, in an object file of their own.
 #include "rownorm_kernels.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -5,6 +5,7 @@
 // Nothing here waits on another workgroup, takes a ticket or lets the arrival order of an atomic decide a result: the only atomics are LDS counts (sums have no order) and
 // one LDS add per (wave, expert, 64-pair step) issued by ONE lane, whose order is the wave's own program order.
 #include "pq_common.h"
+#include "pq_launch.h"
 
 namespace pq {
 

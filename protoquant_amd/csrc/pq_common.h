@@ -25,7 +25,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // switches whatever other host threads set meanwhile, and concurrent launches from several host threads are defined.  Snapshots are never freed
 // (a few hundred bytes per pq_set_option call; tests and experiments only).
 struct Options {
-    int variant = 0;                 // PQ_FORCE_VARIANT (pq_api.hip: enum Variant; 0 = auto)
+    int variant = 0;                 // PQ_FORCE_VARIANT (pq_plan.h: enum Variant; 0 = auto)
     bool no_tailsplit = false, no_splitk = false;
     int force_splitk = 0;
     int fsk = -1;                    // fused split-K: -1 = by plan (fsk_plan), 0 = never, S > 1 = S slices whenever the shape admits them (experiments)

@@ -8,6 +8,7 @@
 // IEEE division, storage-dtype rounding after silu and after the product — bit-identical to oracle/qspec_oracle.c.
 // Algorithmic traffic: read 2 x elem bytes, write 1 B/elem + 4 B/row (+ elem bytes when h is also requested).
 #include "rownorm_kernels.h"
+#include "pq_launch.h"
 
 namespace pq {
 

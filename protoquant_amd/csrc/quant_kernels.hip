@@ -4,6 +4,7 @@
 // reductions.  Arithmetic follows QSPEC v2 exactly (true fp32 division, RNE, no contraction).
 #include <type_traits>
 #include "quant_device.h"
+#include "pq_launch.h"
 
 namespace pq {
 

@@ -1,4 +1,4 @@
-"""CPU: every behaviour switch of libpq_hip.so (kOptionNames, pq_api.hip) is named by at least one GPU test — or sits in EXEMPT below with a reason.
+"""CPU: every behaviour switch of libpq_hip.so (the kOptions table, pq_api.hip) is named by at least one GPU test — or sits in EXEMPT below with a reason.
 
 The header and pq_common.h promise of most switches "time only, never bits"; the A/B tools under tools/ measure with them and the planners' defaults were chosen from
 those measurements.  A switch nobody launches under the suite is compiled device code (or launch geometry) that has never executed there, so a new switch needs a GPU test
@@ -16,9 +16,9 @@ EXEMPT: dict = {}
 
 def _option_names():
     src = open(os.path.join(ROOT, "protoquant_amd", "csrc", "pq_api.hip")).read()
-    m = re.search(r"kOptionNames\[\]\s*=\s*\{(.*?)\};", src, re.S)
-    assert m, "kOptionNames not found in pq_api.hip"
-    names = re.findall(r'"(PQ_[A-Z0-9_]+)"', m.group(1))
+    m = re.search(r"kOptions\[\]\s*=\s*\{(.*?)\n\};", src, re.S)
+    assert m, "the kOptions table was not found in pq_api.hip"
+    names = re.findall(r'^\s*\{"(PQ_[A-Z0-9_]+)",', m.group(1), re.M)
     assert len(names) >= 30 and len(set(names)) == len(names), names
     return names
 
@@ -38,11 +38,18 @@ def test_every_switch_is_named_by_a_gpu_test():
         assert isinstance(why, str) and len(why) > 20, f"EXEMPT[{n}] needs a written reason"
 
 
-def test_every_switch_apply_branch_is_in_the_name_table():
-    """apply_option() knows exactly the names of kOptionNames: a branch without a table entry would be a switch the environment pass (and this guard) never sees."""
-    src = open(os.path.join(ROOT, "protoquant_amd", "csrc", "pq_api.hip")).read()
-    body = src[src.index("bool apply_option("):src.index("const pq::Options* live_options()")]
-    assert sorted(re.findall(r'strcmp\(name, "(PQ_[A-Z0-9_]+)"\)', body)) == sorted(_option_names())
+def test_the_library_knows_exactly_the_table_names():
+    """The environment pass and pq_set_option walk ONE table, so a switch cannot be known to one and not the other; what is left to hold is that the names this guard
+    reads from the source are the names the built library answers to: each is accepted, an unknown one is refused by name, and they are unique and at least 30."""
+    from protoquant_amd import _lib
+    L = _lib.lib()
+    names = _option_names()
+    assert len(names) >= 30 and len(set(names)) == len(names), names
+    for n in names:
+        assert L.pq_set_option(n.encode(), b"") == 0, (n, L.pq_last_error())      # PQ_OK; "" restores the default
+    for bogus in ("PQ_NO_SUCH_SWITCH", names[0] + "_", names[0][:-1], ""):
+        assert L.pq_set_option(bogus.encode(), b"") == 1, bogus                   # PQ_ERR_BAD_ARG
+        assert b"unknown option" in L.pq_last_error(), L.pq_last_error()
 
 
 def _traced_kernels():
