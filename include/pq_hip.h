@@ -180,6 +180,32 @@ int32_t pq_add_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* 
 int32_t pq_act_quant_rowwise(const void* x, int64_t ld_x, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q, float* scale,
                              void* h_out, int64_t ld_h, void* stream);
 
+/* K1ng — K1 fused into GemmaRMSNorm (Gemma, Gemma-2, Gemma-3): quantize(((x.float() * rsqrt(mean(x.float()^2) + eps)) * (1.0 + weight.float())).to(dtype)) per token in
+ * one pass.  Arguments, layouts and the PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise; `weight` is the STORED weight w, the gain is 1 + w.  Numerics, QSPEC
+ * NG1-NG6: the sum of squares and rs exactly as N1-N4, then g = 1.0f + f32(w) and h = cast_rne((f32(x) * rs) * g), every operation rounded in
+ * binary32, no contraction, ONE storage rounding (pq_rmsnorm_quant_rowwise rounds x * rs to the storage dtype first: 1 + w folded into its weight gives other bits);
+ * then Q1-Q6 on the rows of h.
+ * q, scale and h_out may overlap neither x, weight nor each other.  A null x / weight / q / scale, ld < cols, cols >= 2^24, a negative or non-finite eps and an unknown
+ * dtype are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or written, returns PQ_OK. */
+int32_t pq_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q,
+                                       float* scale, void* h_out, int64_t ld_h, void* stream);
+
+/* K1ang — the residual add fused into pq_gemma_rmsnorm_quant_rowwise: sum_out = cast_rne(f32(x) + f32(residual)) is STORED (QSPEC A1) and its rows AS STORED go through
+ * NG1-NG6 and Q1-Q6.  Arguments, aliasing (sum_out may BE x or residual: same pointer and leading dimension), checks and no-op cases as pq_add_rmsnorm_quant_rowwise;
+ * every output holds the bits of the add followed by pq_gemma_rmsnorm_quant_rowwise. */
+int32_t pq_add_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
+                                           int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
+/* K1gg — K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
+ * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
+ * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6
+ * on the rows of h — the eager chain op for op (the activation is stored, then multiplied).  kind: PQ_ACT_GELU_TANH only; anything else is PQ_ERR_BAD_ARG naming `kind`.
+ * h_out (nullable, ld_h): also store h.  q, scale and h_out may overlap neither g, u nor each other.  An unknown dtype, a null g / u / q / scale, negative sizes and
+ * ld < cols are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or written, returns PQ_OK.  Row
+ * layouts as pq_silu_mul_quant_rowwise (PQ_SILU_TPR included: time only, never bits). */
+int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q,
+                                  float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* dequantize(): out[r,c] = cast_rne(f32(q[r,c]) * scale[axis==0 ? c : r]).  `axis` is the axis the
  * scale was reduced over (1: one scale per row, 0: one scale per column).   QSPEC D1. */
 int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t axis,

@@ -457,6 +457,53 @@ int32_t pq_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* re
     return check_launch(fn);
 }
 
+int32_t pq_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q,
+                                       float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:gemma_rmsnorm_quant (K1ng)");
+    const char* fn = "pq_gemma_rmsnorm_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const RowOperand ops[] = {{"x", x, R_IN, "ld_x", ld_x, eb, ""},  {"weight", weight, R_IN, nullptr, cols, eb, ""}, {"q", q, R_OUT, "ld_q", ld_q, 1, ""},
+                              {"scale", scale, R_OUT, nullptr, rows, 4, ""}, {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, &eps, ops, 5, &empty); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::gemma_rmsnorm_quant_dispatch<dt>(x, ld_x, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
+    return check_launch(fn);
+}
+
+int32_t pq_add_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
+                                           int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:add_gemma_rmsnorm_quant (K1ang)");
+    const char* fn = "pq_add_gemma_rmsnorm_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const RowOperand ops[] = {{"x", x, R_IN, "ld_x", ld_x, eb, ""},           {"residual", residual, R_IN, "ld_r", ld_r, eb, ""}, {"sum_out", sum_out, R_INOUT, "ld_s", ld_s, eb, kSumNote},
+                              {"weight", weight, R_IN, nullptr, cols, eb, ""}, {"q", q, R_OUT, "ld_q", ld_q, 1, ""},               {"scale", scale, R_OUT, nullptr, rows, 4, ""},
+                              {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, &eps, ops, 7, &empty); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::add_gemma_rmsnorm_quant_dispatch<dt>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
+    return check_launch(fn);
+}
+
+int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q,
+                                  float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:gelu_mul_quant (K1gg)");
+    const char* fn = "pq_gelu_mul_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    if (kind != PQ_ACT_GELU_TANH) return fail(PQ_ERR_BAD_ARG, "%s: unsupported kind %d (1 = gelu_tanh is the only gated GELU)", fn, kind);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const RowOperand ops[] = {{"g", g, R_IN, "ld_g", ld_g, eb, ""},          {"u", u, R_IN, "ld_u", ld_u, eb, ""}, {"q", q, R_OUT, "ld_q", ld_q, 1, ""},
+                              {"scale", scale, R_OUT, nullptr, rows, 4, ""}, {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, nullptr, ops, 5, &empty); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::gelu_mul_quant_dispatch<dt>(g, ld_g, u, ld_u, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
+    return check_launch(fn);
+}
+
 int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight, const void* bias, float eps, int32_t dtype, int64_t rows, int64_t cols,
                                    int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
     Range range_("pq:layernorm_quant (K1l)");

@@ -35,6 +35,13 @@ template <int DT> void layernorm_quant_dispatch(const void* x, int64_t ldx, cons
                                                 float* scale, void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void add_layernorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, const void* bias,
                                                     float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
+// ---- gemma_norm_kernels.hip, add_gemma_norm_kernels.hip, geglu_kernels.hip: the Gemma forms (K1ng, K1ang, K1gg)
+template <int DT> void gemma_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
+                                                    void* h_out, int64_t ldh, hipStream_t st);
+template <int DT> void add_gemma_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, float eps,
+                                                        int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
+template <int DT> void gelu_mul_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
+                                               void* h_out, int64_t ldh, hipStream_t st);
 
 // ---- the GEMMs (K3 + K4): gemm_s8_generic.hip, gemm_s8_skinny.hip, gemm_s8_ring.hip, gemm_s8_fast.hip
 template <int OUT> void launch_gemm_generic(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb, const EpiArgs& epi, int64_t M, int64_t N, int64_t K, hipStream_t st);

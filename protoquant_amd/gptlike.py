@@ -143,12 +143,14 @@ class _Standin:
     activation) is the real one; any other module is a nested stand-in running ITS class's forward.  Every other attribute is the real module's, methods re-bound
     to the stand-in."""
 
-    def __init__(self, mod: nn.Module, rec: _Record, norms=(), acts=()):
+    def __init__(self, mod: nn.Module, rec: _Record, norms=(), acts=(), cpu_state: bool = False):
         d = self.__dict__
-        d["_mod"], d["_rec"], d["_norms"], d["_acts"], d["_kids"] = mod, rec, dict(norms), dict(acts), {}
+        d["_mod"], d["_rec"], d["_norms"], d["_acts"], d["_kids"], d["_cpu_state"] = mod, rec, dict(norms), dict(acts), {}, cpu_state
 
     def __getattr__(self, name):
         v = getattr(self.__dict__["_mod"], name)
+        if self.__dict__["_cpu_state"] and isinstance(v, torch.Tensor) and v.device.type != "cpu":
+            return v.detach().cpu()          # (cpu_state: a parameter the forward reads itself — Gemma-3's q_norm weight — meets the probe's CPU tensors as a CPU copy)
         if isinstance(v, nn.Module):
             kids = self.__dict__["_kids"]
             if name not in kids:
@@ -201,7 +203,7 @@ class _Standin:
             raise _ProbeRefused(f"forward reads the container {name!r}")
         if _stateless(v):
             return v
-        return _Standin(v, rec)
+        return _Standin(v, rec, cpu_state=self.__dict__["_cpu_state"])
 
 
 def _leaks(out) -> bool:
@@ -214,9 +216,10 @@ def _leaks(out) -> bool:
     return False
 
 
-def _run_probe(mod: nn.Module, rec: _Record, norms=(), acts=(), width: int | None = None):
+def _run_probe(mod: nn.Module, rec: _Record, norms=(), acts=(), width: int | None = None, cpu_state: bool = False):
     """type(mod).forward on a stand-in of `mod` with a [1, 3, width] CPU tensor of zeros; parameters of the forward that have no default get None, one named
-    position_embeddings gets a (cos, sin) pair that broadcasts against any head size.  Raises whatever the forward raises."""
+    position_embeddings gets a (cos, sin) pair that broadcasts against any head size.  Raises whatever the forward raises.  cpu_state: tensors that the stand-ins
+    hand out as attributes of a module on another device are CPU copies (the default hands out the module's own: such a forward raises and is refused)."""
     ps = list(inspect.signature(type(mod).forward).parameters.values())[1:]
     if not ps:
         raise _ProbeRefused("forward takes no input")
@@ -228,23 +231,26 @@ def _run_probe(mod: nn.Module, rec: _Record, norms=(), acts=(), width: int | Non
         elif p.default is p.empty and p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY):
             kw[p.name] = None
     with torch.no_grad(), torch.random.fork_rng(devices=[]):
-        return _Standin(mod, rec, norms, acts)(x, **kw)
+        return _Standin(mod, rec, norms, acts, cpu_state)(x, **kw)
 
 
-def fusable_norms(block: nn.Module) -> list:
+def fusable_norms(block: nn.Module, candidate=None) -> list:
     """Names of the LayerNorm children of `block` that may become LayerNormQuant: each is an nn.LayerNorm with nn.LayerNorm's own forward, a 1-D
     normalized_shape and affine parameters, AND the block's own forward, run on the CPU against stand-ins, calls it exactly once, uses its output for nothing but
     .shape / .device and as the input of int8 projections (at least one), and does not return it.  All candidates of a block are probed in one run; when that run does not accept all of them, each is probed
-    alone (its siblings returning plain tensors) and the survivors once more together."""
-    cands = {n: m for n, m in block.named_children() if _is_eligible_layernorm(m)}
+    alone (its siblings returning plain tensors) and the survivors once more together.
+    candidate (default: the LayerNorm test above): another predicate on a child module — gemma.is_gemma_rmsnorm — selects the norms to probe instead; a candidate
+    has a 1-D `weight`, whose length is the probe's width.  With a candidate the probe also reads the state of a model that lives on a GPU through CPU copies
+    (Gemma-3's attention applies q_norm / k_norm, modules with a weight of their own): the same answer wherever the model is."""
+    cands = {n: m for n, m in block.named_children() if (_is_eligible_layernorm(m) if candidate is None else candidate(m))}
     if not cands:
         return []
-    width = next(iter(cands.values())).normalized_shape[0]
+    width = next(iter(cands.values())).weight.shape[0]
 
     def run(under_test):
         rec = _Record()
         try:
-            out = _run_probe(block, rec, norms={n: ("probe" if n in under_test else "plain") for n in cands}, width=width)
+            out = _run_probe(block, rec, norms={n: ("probe" if n in under_test else "plain") for n in cands}, width=width, cpu_state=candidate is not None)
         except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
             return []
         if _leaks(out):

@@ -270,7 +270,8 @@ def _rf_clear_hook(mod, args, output):
         layer._rf_inbox.clear()
 
 
-def _fuse_residual(model: nn.Module) -> int:
+def _fuse_residual(model: nn.Module, only=None) -> int:
+    """only (default: every layer): the ids of the layers that may be changed — gemma.fuse_gemma_layers passes the layers it recognised"""
     n = 0
     for owner in list(model.modules()):
         for _, stack in list(owner.named_children()):
@@ -278,7 +279,7 @@ def _fuse_residual(model: nn.Module) -> int:
                 continue
             fresh = []
             for layer in stack:
-                if isinstance(layer, ResidualFusedLayer) or not all(hasattr(layer, c) for c in _CHILDREN):
+                if isinstance(layer, ResidualFusedLayer) or not all(hasattr(layer, c) for c in _CHILDREN) or (only is not None and id(layer) not in only):
                     continue
                 if not (isinstance(layer.input_layernorm, RMSNormQuant) and isinstance(layer.post_attention_layernorm, RMSNormQuant)):
                     continue

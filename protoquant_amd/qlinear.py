@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .qtensor import QTensor, quantize, silu_mul_quantize
+from .qtensor import QTensor, gelu_mul_quantize, quantize, silu_mul_quantize
 
 
 def int_mm(xq: torch.Tensor, wq: torch.Tensor) -> torch.Tensor:
@@ -533,13 +533,18 @@ class FusedQLinear(_KPadded, nn.Module):
 class GatedMLP(nn.Module):
     """The gated MLP block of BASELINE config 3 on the int8 path: down(silu(gate(x)) * up(x)).
     gate and up share one activation quantisation and one GEMM launch (FusedQLinear); silu*mul is fused into the
-    quantisation of down's input (silu_mul_quantize), so between the two GEMMs only int8 codes + row scales exist."""
+    quantisation of down's input (silu_mul_quantize), so between the two GEMMs only int8 codes + row scales exist.
+    act="gelu_tanh" (Gemma's GeGLU; gemma.fuse_gemma_layers builds it) puts gelu_mul_quantize in silu_mul_quantize's place."""
 
-    def __init__(self, gate_up: FusedQLinear, down: qlinear):
+    ACTS = ("silu", "gelu_tanh")
+
+    def __init__(self, gate_up: FusedQLinear, down: qlinear, act: str = "silu"):
         super().__init__()
         if len(gate_up.splits) != 2 or gate_up.splits[0] != gate_up.splits[1] or gate_up.splits[0] != down.in_features:
             raise ValueError("GatedMLP: gate and up must both map to down.in_features")
-        self.gate_up, self.down = gate_up, down
+        if act not in self.ACTS:
+            raise ValueError(f"GatedMLP: unknown act {act!r}, expected one of {self.ACTS}")
+        self.gate_up, self.down, self.act = gate_up, down, act
 
     @classmethod
     def from_linears(cls, gate: nn.Linear, up: nn.Linear, down: nn.Linear) -> "GatedMLP":
@@ -547,7 +552,12 @@ class GatedMLP(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         g, u = self.gate_up(x)
+        if self.act == "gelu_tanh":          # Gemma's GeGLU: down(gelu_tanh(gate(x)) * up(x)), kernel K1gg
+            return self.down(gelu_mul_quantize(g, u))
         return self.down(silu_mul_quantize(g, u))
+
+    def extra_repr(self):
+        return "" if self.act == "silu" else f"act={self.act}"
 
 
 def _is_silu(act) -> bool:

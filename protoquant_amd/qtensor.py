@@ -391,6 +391,94 @@ def act_quantize(x: torch.Tensor, kind: str, return_h: bool = False):
     return (qt, h.reshape(x.shape)) if return_h else qt
 
 
+def _check_norm_weight(what: str, x: torch.Tensor, weight: torch.Tensor):
+    if x.dim() < 1 or weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} needs a weight of shape ({x.shape[-1] if x.dim() else '?'},) "
+                         f"and the same dtype/device, got {tuple(weight.shape)} {weight.dtype}")
+
+
+def gemma_rmsnorm_quantize(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, return_h: bool = False):
+    """quantize(((x.float() * rsqrt(mean(x.float()**2, -1) + eps)) * (1.0 + weight.float())).to(x.dtype), axis=-1) in ONE pass (kernel K1ng: K1 fused into
+    GemmaRMSNorm — Gemma, Gemma-2, Gemma-3).  `weight` is the module's STORED weight w; the gain is 1 + w.  Numerics: QSPEC NG1-NG6 (N1-N4's pinned reduction
+    order, then binary32 throughout and ONE storage rounding — rmsnorm_quantize with 1 + w as its weight gives other bits) then Q1-Q6.  return_h=True also returns
+    the normalised activation in the input dtype (stored by the same kernel)."""
+    L.require_gpu(x, "gemma_rmsnorm_quantize(x)")
+    L.require_gpu(weight, "gemma_rmsnorm_quantize(weight)")
+    _check_norm_weight("gemma_rmsnorm_quantize", x, weight)
+    code = L.dtype_code(x.dtype)
+    x2 = _rows_view(x)
+    w = weight.contiguous()
+    rows, cols = x2.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device) if cols > 0 else torch.ones((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_gemma_rmsnorm_quant_rowwise(x2.data_ptr(), L.ld(x2), w.data_ptr(), float(eps), code, rows, cols, q.data_ptr(), max(cols, 1),
+                                                       scale.data_ptr(), h.data_ptr() if return_h else None, max(cols, 1), L.stream_ptr(x)), "gemma_rmsnorm_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, h.reshape(x.shape)) if return_h else qt
+
+
+def add_gemma_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, out: torch.Tensor | None = None,
+                               return_h: bool = False):
+    """summed = residual + x, then gemma_rmsnorm_quantize(summed, weight, eps) — in ONE kernel (K1ang).  Returns (QTensor, summed) or (QTensor, summed, h) with
+    return_h=True; every one of them holds the bits of gemma_rmsnorm_quantize(residual + x, weight, eps, return_h=True) with the add done by torch (QSPEC A1, then
+    NG1-NG6, Q1-Q6).  x and residual have the same shape, dtype and device.  `out` (optional, the same shape and dtype) receives the sum and may be x or residual
+    themselves; any other tensor that overlaps an input is refused.  `summed` has x's shape."""
+    L.require_gpu(x, "add_gemma_rmsnorm_quantize(x)")
+    L.require_gpu(residual, "add_gemma_rmsnorm_quantize(residual)")
+    L.require_gpu(weight, "add_gemma_rmsnorm_quantize(weight)")
+    if x.dim() < 1 or x.shape != residual.shape or x.dtype != residual.dtype or x.device != residual.device:
+        raise ValueError(f"add_gemma_rmsnorm_quantize: x {tuple(x.shape)} {x.dtype} {x.device} and residual {tuple(residual.shape)} {residual.dtype} {residual.device} must match")
+    _check_norm_weight("add_gemma_rmsnorm_quantize", x, weight)
+    if out is not None:
+        L.require_gpu(out, "add_gemma_rmsnorm_quantize(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"add_gemma_rmsnorm_quantize: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, "add_gemma_rmsnorm_quantize")
+    if rows == 0 or cols == 0:          # nothing to add: the empty sum through K1ng (scales of empty rows are 1, QSPEC Q3)
+        res = gemma_rmsnorm_quantize(summed, weight, eps, return_h)
+        return (res[0], summed, res[1]) if return_h else (res, summed)
+    w = weight.contiguous()
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_add_gemma_rmsnorm_quant_rowwise(x2.data_ptr(), L.ld(x2), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2), w.data_ptr(), float(eps), code, rows,
+                                                           cols, q.data_ptr(), cols, scale.data_ptr(), h.data_ptr() if return_h else None, cols, L.stream_ptr(x)),
+                "add_gemma_rmsnorm_quantize")
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
+
+
+def gelu_mul_quantize(g: torch.Tensor, u: torch.Tensor, kind: str = "gelu_tanh", return_h: bool = False):
+    """quantize(F.gelu(g, approximate="tanh") * u, axis=-1) in ONE pass (kernel K1gg): the activation of the down projection of a GeGLU MLP (Gemma's
+    down(act_fn(gate(x)) * up(x))) is computed, reduced and encoded in registers.  g and u may be the column halves of one fused gate+up output.  Numerics: QSPEC
+    GG1-GG3 — act_quantize's tanh GELU (U2) rounded to the input dtype, then the product rounded once, as the eager chain stores them — then Q1-Q6.  kind:
+    "gelu_tanh" only.  return_h=True also returns h in the input dtype (stored by the same kernel)."""
+    L.require_gpu(g, "gelu_mul_quantize(g)")
+    L.require_gpu(u, "gelu_mul_quantize(u)")
+    if kind != "gelu_tanh":
+        raise ValueError(f"gelu_mul_quantize: unsupported kind {kind!r}, expected 'gelu_tanh'")
+    if g.shape != u.shape or g.dtype != u.dtype or g.device != u.device or g.dim() < 1:
+        raise ValueError(f"gelu_mul_quantize: g {tuple(g.shape)} {g.dtype} and u {tuple(u.shape)} {u.dtype} must match")
+    code = L.dtype_code(g.dtype)
+    g2, u2 = _rows_view(g), _rows_view(u)
+    rows, cols = g2.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=g.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=g.device) if cols > 0 else torch.ones((rows,), dtype=torch.float32, device=g.device)
+    h = torch.empty((rows, cols), dtype=g.dtype, device=g.device) if return_h else None
+    with torch.cuda.device(g.device):
+        L.check(L.lib().pq_gelu_mul_quant_rowwise(g2.data_ptr(), L.ld(g2), u2.data_ptr(), L.ld(u2), code, rows, cols, L.ACT_KINDS[kind], q.data_ptr(), max(cols, 1),
+                                                  scale.data_ptr(), h.data_ptr() if return_h else None, max(cols, 1), L.stream_ptr(g)), "gelu_mul_quantize")
+    qt = QTensor(q.reshape(g.shape), scale, 1, g.dtype, g.shape)
+    return (qt, h.reshape(g.shape)) if return_h else qt
+
+
 def dequantize(q: QTensor, dtype: torch.dtype | None = None) -> torch.Tensor:
     """cast_rne(f32(int_data) * scale) along the kept axis -> `dtype` (default: the original dtype)."""
     dtype = dtype or q.orig_dtype
