@@ -196,6 +196,24 @@ int32_t pq_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* 
 int32_t pq_add_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, float eps,
                                            int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
 
+/* K1pang — the sandwich residual flow of Gemma-2 / Gemma-3 in one launch: the post-norm of the sublayer output, the residual add, the next norm and K1.  Per row, with x the
+ * sublayer output and residual the residual stream (QSPEC PN1, A1, NG1-NG6, Q1-Q6):
+ *   p = cast_rne((f32(x) * rs_p) * (1.0f + f32(post_weight)))   NG1-NG5 on x with post_weight / post_eps; ROUNDED to the storage dtype, never written to memory
+ *   sum_out = cast_rne(f32(residual) + f32(p))                  STORED: the new residual stream (A1)
+ *   then NG1-NG6 and Q1-Q6 on the rows of sum_out AS STORED, with weight / eps -> q, scale, optionally h_out.
+ * Every output holds the bits of pq_gemma_rmsnorm_quant_rowwise(x, post_weight, post_eps) with h_out, a correctly rounded add of its h to residual, and
+ * pq_gemma_rmsnorm_quant_rowwise(sum, weight, eps).  post_weight, weight: [cols] of `dtype` (the STORED weights w; the gains are 1 + w).  Row layouts and the
+ * PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time only, never bits).
+ * K1pa, the add-only form: weight == q == scale == h_out == NULL stops after the add and stores sum_out alone (eps is not read).  A partly-null group is PQ_ERR_BAD_ARG
+ * naming the missing argument.
+ * Aliasing: sum_out may BE x or residual (same pointer and leading dimension; the whole row of x is read before any of sum_out is written); any other overlap of
+ * sum_out with an input, and any overlap of q, scale or h_out with an input, sum_out or each other, is refused.  A null x / post_weight / residual / sum_out, ld < cols,
+ * cols >= 2^24, a negative or non-finite eps or post_eps and an unknown dtype are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.
+ * rows == 0 or cols == 0: nothing is read or written, returns PQ_OK (the scales of empty rows are 1, QSPEC Q3: the caller's). */
+int32_t pq_gemma_postnorm_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* post_weight, float post_eps, const void* residual, int64_t ld_r, void* sum_out,
+                                                    int64_t ld_s, const void* weight, float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale,
+                                                    void* h_out, int64_t ld_h, void* stream);
+
 /* K1gg — K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6

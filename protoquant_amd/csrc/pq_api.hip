@@ -254,16 +254,17 @@ struct RowOperand {
 };
 const char kSumNote[] = " (the sum is the new residual stream: it is always stored)", kAffineNote[] = " (a LayerNorm without affine parameters is not supported)";
 
-// The checks of a row producer after its dtype (and kind), in this order: shape, eps (`eps` is null for a producer without a norm: no eps, no 2^24 bound on cols), the leading
+// The checks of a row producer after its dtype (and kind), in this order: shape, eps (`eps` is null for a producer without a norm: no eps, no 2^24 bound on cols; `post_eps`: the second eps of K1pang, checked after it), the leading
 // dimensions in operand order, the empty problem (*empty: nothing to launch), the null pointers in operand order, then the overlaps.  An output may overlap neither an
 // input nor another output: the vector layouts load a clamped duplicate of a row's last vector into the slots past its end and the generic kernels read x again in every
 // pass, so an in-place h_out is not tolerated.  An in-out operand (sum_out) may BE a matrix input (same base and pitch: every element is read before it is written, by the
 // thread that writes it); any other overlap with an input is refused, and for the outputs it counts as the last of the inputs.
-int32_t check_row_producer(const char* fn, int64_t rows, int64_t cols, const float* eps, const RowOperand* ops, int n, bool* empty) {
+int32_t check_row_producer(const char* fn, int64_t rows, int64_t cols, const float* eps, const RowOperand* ops, int n, bool* empty, const float* post_eps = nullptr) {
     *empty = false;
     if (!eps && (rows < 0 || cols < 0)) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld)", fn, (long long)rows, (long long)cols);
     if (eps && (rows < 0 || cols < 0 || cols >= (1 << 24))) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld; cols < 2^24)", fn, (long long)rows, (long long)cols);
     if (eps && (!(*eps >= 0.0f) || *eps > 3.4028234e38f)) return fail(PQ_ERR_BAD_ARG, "%s: eps must be finite and >= 0 (eps=%g)", fn, (double)*eps);
+    if (post_eps && (!(*post_eps >= 0.0f) || *post_eps > 3.4028234e38f)) return fail(PQ_ERR_BAD_ARG, "%s: post_eps must be finite and >= 0 (post_eps=%g)", fn, (double)*post_eps);
     for (int i = 0; i < n; ++i)
         if (ops[i].ld_name && (ops[i].null_note || ops[i].p) && ops[i].ld < cols)
             return fail(PQ_ERR_BAD_ARG, "%s: %s %lld < cols %lld", fn, ops[i].ld_name, (long long)ops[i].ld, (long long)cols);
@@ -485,6 +486,33 @@ int32_t pq_add_gemma_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const vo
     if (const int32_t rc = check_row_producer(fn, rows, cols, &eps, ops, 7, &empty); rc || empty) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::add_gemma_rmsnorm_quant_dispatch<dt>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
+    return check_launch(fn);
+}
+
+int32_t pq_gemma_postnorm_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* post_weight, float post_eps, const void* residual, int64_t ld_r, void* sum_out,
+                                                    int64_t ld_s, const void* weight, float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale,
+                                                    void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:gemma_postnorm_add_rmsnorm_quant (K1pang / K1pa)");
+    const char* fn = "pq_gemma_postnorm_add_rmsnorm_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const bool add_only = !weight && !q && !scale && !h_out;          // K1pa: the whole quantisation group is absent (then eps is not read)
+    const char* group = " (weight, q and scale go together: all three and h_out null is the add-only form)";
+    const RowOperand ops[] = {{"x", x, R_IN, "ld_x", ld_x, eb, ""},
+                              {"post_weight", post_weight, R_IN, nullptr, cols, eb, ""},
+                              {"residual", residual, R_IN, "ld_r", ld_r, eb, ""},
+                              {"sum_out", sum_out, R_INOUT, "ld_s", ld_s, eb, kSumNote},
+                              {"weight", weight, R_IN, nullptr, cols, eb, group},
+                              {"q", q, R_OUT, "ld_q", ld_q, 1, group},
+                              {"scale", scale, R_OUT, nullptr, rows, 4, group},
+                              {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    const float no_eps = 0.0f;
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, add_only ? &no_eps : &eps, ops, add_only ? 4 : 8, &empty, &post_eps); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) {
+        pq::gemma_postnorm_add_rmsnorm_quant_dispatch<dt>(x, ld_x, post_weight, post_eps, residual, ld_r, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st);
+    });
     return check_launch(fn);
 }
 

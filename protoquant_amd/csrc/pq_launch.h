@@ -35,11 +35,15 @@ template <int DT> void layernorm_quant_dispatch(const void* x, int64_t ldx, cons
                                                 float* scale, void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void add_layernorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, const void* bias,
                                                     float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
-// ---- gemma_norm_kernels.hip, add_gemma_norm_kernels.hip, geglu_kernels.hip: the Gemma forms (K1ng, K1ang, K1gg)
+// ---- gemma_norm_kernels.hip, add_gemma_norm_kernels.hip, geglu_kernels.hip, gemma_postnorm_kernels.hip: the Gemma forms (K1ng, K1ang, K1gg, K1pang / K1pa)
 template <int DT> void gemma_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
                                                     void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void add_gemma_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, float eps,
                                                         int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
+// (wgt == nullptr: the add-only form K1pa — q, scale and h_out are null as well)
+template <int DT> void gemma_postnorm_add_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* pwgt, float post_eps, const void* res, int64_t ldr, void* sum_out,
+                                                                 int64_t lds, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
+                                                                 void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void gelu_mul_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
                                                void* h_out, int64_t ldh, hipStream_t st);
 

@@ -7,7 +7,14 @@
 * q / k / v share one quantisation and one GEMM launch, as ``fuse_llama_layers`` does it (its code runs);
 * the GeGLU MLP, ``down(gelu_tanh(gate(x)) * up(x))``, becomes ``GatedMLP(act="gelu_tanh")``: a fused gate+up GEMM and ``gelu_mul_quantize`` (kernel K1gg);
 * ``fuse_residual=True`` (opt-in): a layer whose forward is the Llama data flow — Gemma v1 — gets its two residual adds taken into the norms that follow them
-  (``add_gemma_rmsnorm_quantize``, kernel K1ang), through ``llama.ResidualFusedLayer``.  Gemma-2 and Gemma-3 normalise the sublayer output BEFORE the add: refused.
+  (``add_gemma_rmsnorm_quantize``, kernel K1ang), through ``llama.ResidualFusedLayer``.  Gemma-2 and Gemma-3 normalise the sublayer output BEFORE the add: refused
+  by that switch;
+* ``fuse_gemma_postnorm_residual(model)`` (opt-in, an entry of its own, after ``fuse_gemma_layers``): a layer whose forward is the sandwich data flow — Gemma-2 and
+  Gemma-3, ``r1 = x + post_attention_layernorm(self_attn(input_layernorm(x)))``, ``out = r1 + post_feedforward_layernorm(mlp(pre_feedforward_layernorm(r1)))`` —
+  becomes a ``SandwichFusedLayer``: each post-norm, the add behind it and the norm + quantisation that follows run in ONE kernel
+  (``gemma_postnorm_add_rmsnorm_quantize``, K1pang; ``gemma_postnorm_add``, K1pa, at the end of a chain).  The post-norms become the specified norm (QSPEC PN1:
+  NG1-NG5, spec-exact and eager-close) instead of the eager chain, so the switch changes bits against the model without it; no eager GemmaRMSNorm is left inside
+  such a layer.
 
 ``swap_linears(model)`` must have run first.  Nothing is recognised by class name: a norm is probed (``is_gemma_rmsnorm`` runs its class's forward against the
 formula), its use is probed (``gptlike.fusable_norms``), the activation is probed (``gptlike.activation_kind``), the MLP's forward is probed.  The embedding
@@ -20,9 +27,9 @@ import torch
 from torch import nn
 
 from .gptlike import activation_kind, fusable_norms
-from .llama import RMSNormQuant, _FusedSlice, _fuse_residual, fuse_llama_layers
+from .llama import RMSNormQuant, _FusedSlice, _HandOver, _ProbeLayer, _forward_extra_params, _fuse_residual, _link_chain, fuse_llama_layers
 from .qlinear import FusedQLinear, GatedMLP, qlinear
-from .qtensor import add_gemma_rmsnorm_quantize, gemma_rmsnorm_quantize
+from .qtensor import add_gemma_rmsnorm_quantize, gemma_postnorm_add, gemma_postnorm_add_rmsnorm_quantize, gemma_rmsnorm_quantize
 
 
 class GemmaRMSNormQuant(RMSNormQuant):
@@ -44,6 +51,20 @@ class GemmaRMSNormQuant(RMSNormQuant):
 
     def extra_repr(self):
         return f"{tuple(self.weight.shape)}, eps={self.eps}, gain 1 + w -> int8 per-token QTensor"
+
+
+class GemmaSandwichNormQuant(GemmaRMSNormQuant):
+    """The GemmaRMSNormQuant of a sandwich-fused layer (fuse_gemma_postnorm_residual gives the two norm objects this class; nothing else about them changes): its
+    forward also takes the post-norm that precedes the residual add.  A class of its own because GemmaRMSNormQuant.forward(x, residual=None) is a held signature."""
+
+    def forward(self, x: torch.Tensor, residual: torch.Tensor | None = None, post_norm=None):
+        """Without `post_norm`: GemmaRMSNormQuant.forward.  With `residual` and `post_norm` (a Gemma norm module: only its `weight` and `eps` are read, it is not
+        called): summed = residual + post_norm(x) by the specified norm (QSPEC PN1), and (QTensor of GemmaRMSNorm(summed), summed) from one kernel (K1pang)."""
+        if post_norm is None:
+            return super().forward(x, residual)
+        if residual is None:
+            raise ValueError("GemmaSandwichNormQuant: post_norm needs the residual its output is added to")
+        return gemma_postnorm_add_rmsnorm_quantize(x, post_norm.weight, residual, self.weight, self.eps, post_norm.eps)
 
 
 # ---------------------------------------------------------------- is it a Gemma norm?  (by behaviour)
@@ -195,4 +216,153 @@ def fuse_gemma_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
         n += int(did)
     if fuse_residual:
         _fuse_residual(model, only=mine)          # the layers recognised above and no others: a Llama layer that fuse_llama_layers prepared is not this call's to change
+    return n
+
+
+# ---------------------------------------------------------------- the sandwich residual flow of Gemma-2 / Gemma-3 (opt-in)
+_SANDWICH = ("input_layernorm", "self_attn", "post_attention_layernorm", "pre_feedforward_layernorm", "mlp", "post_feedforward_layernorm")
+
+
+def residual_flow_is_sandwich(layer: nn.Module, cls=None) -> bool:
+    """True iff `cls.forward` (default: the layer's own class) IS the sandwich data flow on this layer:
+
+        r1  = x  + post_attention_layernorm(self_attn(hidden_states=input_layernorm(x), **kwargs)[0])
+        out = r1 + post_feedforward_layernorm(mlp(pre_feedforward_layernorm(r1)))
+
+    with each of the six children called once, the attention given its input as `hidden_states=` (the form the fused layer calls it in; a positional hidden state is
+    refused), every keyword argument of the layer handed to it unchanged, no other submodule touched and a tensor
+    returned.  Probed like llama.residual_flow_is_llama, not pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a
+    tiny CPU tensor, and its result must EQUAL the formula.  transformers' Gemma2DecoderLayer and Gemma3DecoderLayer pass; Gemma v1 and Llama (no post-norms),
+    OLMo-2 (post-norms only), Gemma-3n (further submodules) and any forward that raises on the stand-in do not."""
+    cls = cls or type(layer)
+    try:
+        names, var_kw = _forward_extra_params(cls)
+    except (TypeError, ValueError, AttributeError):
+        return False
+    given = {n: object() for n in names}
+    if var_kw:
+        given["pq_probe_extra"] = object()
+    calls = {c: 0 for c in _SANDWICH}
+    seen = {}
+
+    def counted(name, f):
+        def run(t):
+            calls[name] += 1
+            return f(t)
+        return run
+
+    def attn(*a, **kw):          # (SandwichFusedLayer calls self_attn(hidden_states=h, **kwargs): that form and no other is accepted)
+        calls["self_attn"] += 1
+        h = kw.pop("hidden_states")
+        seen["positional"], seen["kwargs"] = len(a), kw
+        return h + 1.0, None
+
+    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
+    probe = _ProbeLayer(layer, {"input_layernorm": counted("input_layernorm", lambda t: t * 2.0), "self_attn": attn,
+                                "post_attention_layernorm": counted("post_attention_layernorm", lambda t: t * 3.0 - 1.0),
+                                "pre_feedforward_layernorm": counted("pre_feedforward_layernorm", lambda t: t * 0.5 - 3.0), "mlp": counted("mlp", lambda t: t * t),
+                                "post_feedforward_layernorm": counted("post_feedforward_layernorm", lambda t: t * 4.0 + 5.0)})
+    try:
+        with torch.no_grad():
+            out = cls.forward(probe, x.clone(), **given)
+    except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
+        return False
+    if not isinstance(out, torch.Tensor) or any(n != 1 for n in calls.values()):
+        return False
+    kw = seen["kwargs"]
+    if seen["positional"] != 0 or set(kw) != set(given) or any(kw[k] is not given[k] for k in given):
+        return False
+    r1 = x + ((x * 2.0 + 1.0) * 3.0 - 1.0)
+    want = r1 + ((r1 * 0.5 - 3.0) ** 2 * 4.0 + 5.0)
+    return out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+
+
+class SandwichFusedLayer(nn.Module):
+    """A sandwich-flow decoder layer (Gemma-2, Gemma-3) whose two post-norms and residual adds run inside the norm + quantisation kernels that follow them (K1pang,
+    gemma_postnorm_add_rmsnorm_quantize; K1pa, gemma_postnorm_add, at the end of a chain):
+
+        h        = the QTensor handed over for this very tensor, else input_layernorm(hidden)
+        a        = self_attn(hidden_states=h, **kwargs)[0]
+        hq, r1   = pre_feedforward_layernorm(a, residual=hidden, post_norm=post_attention_layernorm)       # post-norm + add + norm + quant, one launch
+        m        = mlp(hq)
+        last of the chain:  return gemma_postnorm_add(m, pfn.weight, r1, pfn.eps)                          # post-norm + add, one launch; pfn = post_feedforward_layernorm
+        otherwise:          hq2, out = NEXT layer's input_layernorm(m, residual=r1, post_norm=pfn);  hand hq2 to the next layer;  return out
+
+    What the layer returns is the real summed tensor, so hooks, output_hidden_states and the final norm see a residual stream.  The two post-norm modules stay the
+    model's modules, object for object (state-dict keys unchanged); they are no longer CALLED — only their `weight` and `eps` are read, and the norm is the specified
+    one (QSPEC PN1) instead of the eager chain.  fuse_gemma_postnorm_residual makes a layer one by giving the layer object a class that derives from this one AND
+    from its original class: the object, its children under their names, its other attributes, its hooks and every isinstance check on it stay as they were.  The
+    tensor the layer was called with is never written; the hand-over is consumed at the next layer's entry and never served for another tensor or a tensor changed in
+    place since."""
+    _pq_residual_fused = True
+
+    def forward(self, hidden_states, *args, **kwargs):
+        if args:          # positional arguments of the original forward, by its own parameter names
+            if len(args) > len(self._rf_argnames):
+                raise TypeError(f"{type(self).__name__}.forward takes at most {len(self._rf_argnames) + 1} positional arguments")
+            kwargs.update(zip(self._rf_argnames, args))
+        h = self._rf_inbox.take(hidden_states)
+        if h is None:
+            h = self.input_layernorm(hidden_states)
+        attn_out = self.self_attn(hidden_states=h, **kwargs)[0]
+        hq, r1 = self.pre_feedforward_layernorm(attn_out, residual=hidden_states, post_norm=self.post_attention_layernorm)
+        m = self.mlp(hq)
+        pfn = self.post_feedforward_layernorm
+        nxt = self._rf_next[0]
+        if nxt is None:
+            return gemma_postnorm_add(m, pfn.weight, r1, pfn.eps)
+        hq2, out = nxt.input_layernorm(m, residual=r1, post_norm=pfn)
+        nxt._rf_inbox.put(out, hq2)
+        return out
+
+
+_SF_CLASSES: dict = {}
+
+
+def _sandwich_fused_class(cls):
+    if cls not in _SF_CLASSES:
+        _SF_CLASSES[cls] = type("SandwichFused" + cls.__name__, (SandwichFusedLayer, cls), {"__doc__": SandwichFusedLayer.__doc__})
+    return _SF_CLASSES[cls]
+
+
+def _hooked(m: nn.Module) -> bool:
+    return bool(m._forward_hooks) or bool(m._forward_pre_hooks)
+
+
+def fuse_gemma_postnorm_residual(model: nn.Module) -> int:
+    """Opt-in, after fuse_gemma_layers(model) (which it leaves exactly as it was: a separate entry, so nothing changes for a caller who does not ask): every layer
+    of a ModuleList becomes a SandwichFusedLayer (in place) if ALL of these hold — it has the six children input_layernorm, self_attn, post_attention_layernorm,
+    pre_feedforward_layernorm, mlp and post_feedforward_layernorm; input_layernorm and pre_feedforward_layernorm are GemmaRMSNormQuant (the two objects become
+    GemmaSandwichNormQuant, whose forward also takes the post-norm; weight, eps and state-dict keys stay); both post-norms pass
+    is_gemma_rmsnorm and are as wide as those; neither post-norm has a forward hook or pre-hook registered (the post-norm MODULE is no longer called — the kernel
+    reads its weight and eps — so a hook on it would silently stop firing: such a layer is refused); and the class's forward passes residual_flow_is_sandwich.
+    A refused layer keeps everything it had and breaks the chain: its predecessor ends with K1pa.  The post-norms become the specified norm (QSPEC PN1) instead of
+    the eager chain, so the model's bits change against the model without this switch.  The module that owns the ModuleList gets an always-called forward hook that
+    drops every pending hand-over when its forward ends.  Returns the number of layers changed by THIS call (a second call finds nothing left to change and returns
+    0); llama.residual_fused_layers(model) counts them over all calls."""
+    n = 0
+    for owner in list(model.modules()):
+        for _, stack in list(owner.named_children()):
+            if not isinstance(stack, nn.ModuleList):
+                continue
+            fresh = []
+            for layer in stack:
+                if isinstance(layer, SandwichFusedLayer) or not all(hasattr(layer, c) for c in _SANDWICH):
+                    continue
+                n1, n2 = layer.input_layernorm, layer.pre_feedforward_layernorm
+                if not (isinstance(n1, GemmaRMSNormQuant) and isinstance(n2, GemmaRMSNormQuant)) or n1.weight.shape != n2.weight.shape:
+                    continue
+                posts = (layer.post_attention_layernorm, layer.post_feedforward_layernorm)
+                if not all(is_gemma_rmsnorm(p) and p.weight.shape == n1.weight.shape and not _hooked(p) for p in posts):
+                    continue
+                cls = type(layer)
+                if not residual_flow_is_sandwich(layer, cls):
+                    continue
+                n1.__class__ = n2.__class__ = GemmaSandwichNormQuant          # (the same objects: they learn the post_norm argument)
+                layer._rf_argnames = _forward_extra_params(cls)[0]
+                layer._rf_inbox, layer._rf_next = _HandOver(), [None]
+                layer.__class__ = _sandwich_fused_class(cls)
+                fresh.append(layer)
+            _link_chain(owner, stack, fresh, SandwichFusedLayer)          # (a chain that ends, ends with K1pa)
+            n += len(fresh)
     return n

@@ -270,6 +270,20 @@ def _rf_clear_hook(mod, args, output):
         layer._rf_inbox.clear()
 
 
+def _link_chain(owner: nn.Module, stack: nn.ModuleList, fresh: list, kind: type) -> None:
+    """After `fresh` layers of `stack` became `kind` (ResidualFusedLayer, or gemma.SandwichFusedLayer): (re)link the chain — a layer hands over to its successor in the
+    stack when that one is of the same kind; anything else ends the chain — and give the owner of the stack its clearing hook, once."""
+    for i, layer in enumerate(stack):
+        if isinstance(layer, kind):
+            nxt = stack[i + 1] if i + 1 < len(stack) else None
+            layer._rf_next = [nxt if isinstance(nxt, kind) else None]          # (a list: the next layer is registered once, in the stack)
+    if fresh:
+        if not hasattr(owner, "_rf_layers"):
+            owner._rf_layers = []
+            owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
+        owner._rf_layers.extend(fresh)
+
+
 def _fuse_residual(model: nn.Module, only=None) -> int:
     """only (default: every layer): the ids of the layers that may be changed — gemma.fuse_gemma_layers passes the layers it recognised"""
     n = 0
@@ -290,17 +304,8 @@ def _fuse_residual(model: nn.Module, only=None) -> int:
                 layer._rf_inbox, layer._rf_next = _HandOver(), [None]
                 layer.__class__ = _residual_fused_class(cls)
                 fresh.append(layer)
-            # (re)link the chain: a layer hands over to its successor in the stack when that one is residual-fused too; anything else ends the chain with a torch add
-            for i, layer in enumerate(stack):
-                if isinstance(layer, ResidualFusedLayer):
-                    nxt = stack[i + 1] if i + 1 < len(stack) else None
-                    layer._rf_next = [nxt if isinstance(nxt, ResidualFusedLayer) else None]          # (a list: the next layer is registered once, in the stack)
-            if fresh:
-                if not hasattr(owner, "_rf_layers"):
-                    owner._rf_layers = []
-                    owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
-                owner._rf_layers.extend(fresh)
-                n += len(fresh)
+            _link_chain(owner, stack, fresh, ResidualFusedLayer)          # (a chain that ends, ends with a torch add)
+            n += len(fresh)
     return n
 
 

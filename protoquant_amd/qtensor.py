@@ -455,6 +455,76 @@ def add_gemma_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: 
     return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
 
 
+def _postnorm_operands(what: str, x, post_weight, residual, out):
+    """the shared argument checks of the two sandwich calls; returns (code, x2, r2, rows, cols, summed, s2)"""
+    L.require_gpu(x, f"{what}(x)")
+    L.require_gpu(residual, f"{what}(residual)")
+    L.require_gpu(post_weight, f"{what}(post_weight)")
+    if x.dim() < 1 or x.shape != residual.shape or x.dtype != residual.dtype or x.device != residual.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} {x.device} and residual {tuple(residual.shape)} {residual.dtype} {residual.device} must match")
+    _check_norm_weight(what, x, post_weight)
+    if out is not None:
+        L.require_gpu(out, f"{what}(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"{what}: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    return code, x2, r2, rows, cols, summed, _rows_view_of_out(summed, rows, cols, what)
+
+
+def gemma_postnorm_add_rmsnorm_quantize(x: torch.Tensor, post_weight: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6,
+                                        post_eps: float = 1e-6, out: torch.Tensor | None = None, return_h: bool = False):
+    """The sandwich residual flow of Gemma-2 / Gemma-3 in ONE kernel (K1pang): x is a sublayer's output, `post_weight` / `post_eps` the post-norm on it, `residual` the
+    residual stream, `weight` / `eps` the norm that follows the add.  Returns (QTensor, summed) or (QTensor, summed, h) with return_h=True, and every one of them
+    holds, bit for bit, what this composition gives:
+
+        p      = gemma_rmsnorm_quantize(x, post_weight, post_eps, return_h=True)[1]
+        summed = residual + p
+        QT, h  = gemma_rmsnorm_quantize(summed, weight, eps, return_h=True)
+
+    (QSPEC PN1: p is rounded to the storage dtype and never stored; A1; then NG1-NG6 and Q1-Q6 on the rows of the sum as stored.)  x and residual have the same shape,
+    dtype and device; both weights are the modules' STORED weights.  `out` (optional, the same shape and dtype) receives the sum and may be x or residual themselves;
+    any other tensor that overlaps an input is refused.  `summed` has x's shape."""
+    what = "gemma_postnorm_add_rmsnorm_quantize"
+    code, x2, r2, rows, cols, summed, s2 = _postnorm_operands(what, x, post_weight, residual, out)
+    L.require_gpu(weight, f"{what}(weight)")
+    _check_norm_weight(what, x, weight)
+    if rows == 0 or cols == 0:          # nothing to normalise or add: the empty sum through K1ng (scales of empty rows are 1, QSPEC Q3)
+        res = gemma_rmsnorm_quantize(summed, weight, eps, return_h)
+        return (res[0], summed, res[1]) if return_h else (res, summed)
+    pw, w = post_weight.contiguous(), weight.contiguous()
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_gemma_postnorm_add_rmsnorm_quant_rowwise(x2.data_ptr(), L.ld(x2), pw.data_ptr(), float(post_eps), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2),
+                                                                    w.data_ptr(), float(eps), code, rows, cols, q.data_ptr(), cols, scale.data_ptr(),
+                                                                    h.data_ptr() if return_h else None, cols, L.stream_ptr(x)), what)
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
+
+
+def gemma_postnorm_add(x: torch.Tensor, post_weight: torch.Tensor, residual: torch.Tensor, post_eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:
+    """summed = residual + GemmaRMSNorm(x; post_weight, post_eps) in ONE kernel (K1pa, the add-only form of K1pang: the end of a chain of sandwich-fused layers).
+    Returns `summed`, the bits of
+
+        p      = gemma_rmsnorm_quantize(x, post_weight, post_eps, return_h=True)[1]
+        summed = residual + p
+
+    and of gemma_postnorm_add_rmsnorm_quantize's `summed` (QSPEC PN1, A1).  Arguments and `out` as there."""
+    what = "gemma_postnorm_add"
+    code, x2, r2, rows, cols, summed, s2 = _postnorm_operands(what, x, post_weight, residual, out)
+    if rows == 0 or cols == 0:
+        return summed
+    pw = post_weight.contiguous()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_gemma_postnorm_add_rmsnorm_quant_rowwise(x2.data_ptr(), L.ld(x2), pw.data_ptr(), float(post_eps), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2),
+                                                                    None, 0.0, code, rows, cols, None, cols, None, None, cols, L.stream_ptr(x)), what)
+    return summed
+
+
 def gelu_mul_quantize(g: torch.Tensor, u: torch.Tensor, kind: str = "gelu_tanh", return_h: bool = False):
     """quantize(F.gelu(g, approximate="tanh") * u, axis=-1) in ONE pass (kernel K1gg): the activation of the down projection of a GeGLU MLP (Gemma's
     down(act_fn(gate(x)) * up(x))) is computed, reduced and encoded in registers.  g and u may be the column halves of one fused gate+up output.  Numerics: QSPEC
