@@ -1,7 +1,8 @@
 """Fuzz harness (test infrastructure; run by tests/test_gpu_fuzz.py, or directly: `FUZZ_SECONDS=150 python -m tests.fuzz_quant`):
 random shapes / strides / alignments / special values through quantize (both axes), dequantize, silu_mul_quantize,
 rmsnorm_quantize, the split quantisation halves of the int8-code exchange (random column blocks), the fused GEMM epilogue and the GEMM on stacked
-code blocks, each compared bit for bit with the oracle."""
+code blocks, each compared bit for bit with the oracle.  Three epilogue problems in ten carry special values (NaN, +-Inf, +-0, subnormal, huge, negative) in their
+scales and bias: those compare NaNs as a class (positions must agree) and every other element bit for bit."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -30,6 +31,24 @@ def eqb(got, want, what, ctx, nan_ok=None):
     if g.shape != w.shape or np.count_nonzero(g[m] != w[m]):
         print("MISMATCH", what, ctx); return 1
     return 0
+
+
+def eqf(got, want, code, what, ctx):
+    """a float output that may hold NaNs: the NaN positions agree, every other element is the oracle's bit for bit (QSPEC leaves a NaN's payload and sign open)"""
+    nan = np.isnan(Q.to_f32(want, code))
+    if not np.array_equal(np.isnan(got.detach().float().cpu().numpy()), nan):
+        print("MISMATCH (NaN positions)", what, ctx); return 1
+    return eqb(got, want, what, ctx, nan_ok=nan)
+
+
+def plant(xs, ws):
+    """with probability 0.3 (ONE draw per problem): one to three entries of each scale vector replaced by special values; returns whether it did"""
+    if rng.random() >= 0.3:
+        return False
+    for v in (xs, ws):
+        k = int(rng.integers(1, 4))
+        v[rng.integers(0, v.size, k)] = rng.choice(np.append(SPECIAL, np.float32(0.0)), k)
+    return True
 
 
 def strided(a_np, code, pad, off):
@@ -87,19 +106,23 @@ def run(budget, seed):
       a = rng.integers(-128, 128, (M2, K2), dtype=np.int8); b = rng.integers(-128, 128, (N2, K2), dtype=np.int8)
       acc = (a.astype(np.int32) @ b.astype(np.int32).T)
       xs2 = (rng.random(M2).astype(np.float32) + 1e-3) * float(rng.choice([1e-3, 1.0, 50.0])); ws2 = rng.random(N2).astype(np.float32) * 0.02 + 1e-5
-      bv = Q.from_f32(rng.standard_normal(N2).astype(np.float32), code) if rng.random() < 0.5 else None
+      bf = rng.standard_normal(N2).astype(np.float32) if rng.random() < 0.5 else None
+      odd = plant(xs2, ws2)
+      if odd and bf is not None:
+          bf[int(rng.integers(0, N2))] = rng.choice(SPECIAL)
+      bv = Q.from_f32(bf, code) if bf is not None else None
       want = Q.epilogue(acc, xs2, ws2, bv, code)
       for v in ("", "generic", "ring128", "sp256_16", "ring128x160"):
           _pqlib.set_option("PQ_FORCE_VARIANT", v)
           got = pq.qlinear_s8(torch.from_numpy(a).cuda(), torch.from_numpy(xs2).cuda(), torch.from_numpy(b).cuda(), torch.from_numpy(ws2).cuda(),
                               to_gpu(bv, code) if bv is not None else None, TD[code])
-          bad += eqb(got, want, f"epilogue[{v or 'auto'}]", f"code={code} M={M2} N={N2} K={K2} bias={bv is not None}")
+          bad += eqf(got, want, code, f"epilogue[{v or 'auto'}]", f"code={code} M={M2} N={N2} K={K2} bias={bv is not None} special={odd}")
       _pqlib.set_option("PQ_FORCE_VARIANT", "")
       # round 5: the same product with the activation codes STACKED in G K-slabs (ring tiles walk them in place, everything else takes the layout pass)
       G2 = int(rng.choice([g_ for g_ in (1, 2, 4, 8) if (K2 // 128) % g_ == 0]))
       stk = torch.from_numpy(np.ascontiguousarray(a.reshape(M2, G2, K2 // G2).transpose(1, 0, 2))).cuda()
       got = pq.qlinear_s8_kslabs(stk, torch.from_numpy(xs2).cuda(), torch.from_numpy(b).cuda(), torch.from_numpy(ws2).cuda(), to_gpu(bv, code) if bv is not None else None, TD[code])
-      bad += eqb(got, want, "epilogue[kslabs]", f"code={code} M={M2} N={N2} K={K2} G={G2} bias={bv is not None}")
+      bad += eqf(got, want, code, "epilogue[kslabs]", f"code={code} M={M2} N={N2} K={K2} G={G2} bias={bv is not None} special={odd}")
       # round 6: a FORCED fused split-K (f ticket slices of the 256 x 256 tile) on stacked blocks — slab counts 1 .. 8, slabs of 4 .. 9 K-tiles, slices that cover 1 / 2 / 4 slabs
       # or a share of one: the asm K-loop's activation cursor jumps at the slab boundaries.  Against the int32 matmul + E1-E4 of the numpy oracle.
       if n % 3 == 0:
@@ -110,6 +133,7 @@ def run(budget, seed):
           M3, N3 = int(rng.integers(65, 600)), int(rng.integers(129, 600))
           a3 = rng.integers(-128, 128, (M3, K3), dtype=np.int8); b3 = rng.integers(-128, 128, (N3, K3), dtype=np.int8)
           xs3 = rng.random(M3).astype(np.float32) + 1e-3; ws3 = rng.random(N3).astype(np.float32) * 0.02 + 1e-5
+          odd3 = plant(xs3, ws3)
           want3 = Q.epilogue(a3.astype(np.int32) @ b3.astype(np.int32).T, xs3, ws3, None, code)
           stk3 = torch.from_numpy(np.ascontiguousarray(a3.reshape(M3, G3, K3 // G3).transpose(1, 0, 2))).cuda()
           _pqlib.set_option("PQ_FSK", str(f3))
@@ -117,7 +141,7 @@ def run(budget, seed):
               got3 = pq.qlinear_s8_kslabs(stk3, torch.from_numpy(xs3).cuda(), torch.from_numpy(b3).cuda(), torch.from_numpy(ws3).cuda(), None, TD[code])
           finally:
               _pqlib.set_option("PQ_FSK", "")
-          bad += eqb(got3, want3, "epilogue[kslabs, forced fsk]", f"code={code} M={M3} N={N3} K={K3} G={G3} f={f3}")
+          bad += eqf(got3, want3, code, "epilogue[kslabs, forced fsk]", f"code={code} M={M3} N={N3} K={K3} G={G3} f={f3} special={odd3}")
       n += 1
   print(f"fuzz_quant: {n} problems in {time.time() - t0:.0f} s, mismatches: {bad}")
   return n, bad
