@@ -162,6 +162,24 @@ int32_t pq_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* weig
 int32_t pq_add_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, void* sum_out, int64_t ld_s, const void* weight, const void* bias,
                                        float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
 
+/* K1pl / K1l2 — the parallel residual of a GPT-NeoX (use_parallel_residual) or Phi decoder block, fused into the LayerNorm(s) of the NEXT block:
+ *   sum_out = cast_rne(f32(cast_rne(f32(a) + f32(b))) + f32(c))      QSPEC A2: A1 twice, in THIS association; the inner sum is never stored
+ * then, on the rows of sum_out AS STORED, the mean and the variance of L1-L3 ONCE, and per norm group g = 1, 2 its own L4 (eps_g), L5 (weight_g, bias_g; bias_g
+ * nullable) and L6 = Q1-Q6, in one kernel.  Every output holds the bits of two eager adds in that association followed by pq_layernorm_quant_rowwise per group.
+ * Addition commutes, so a and b may be swapped; the three may not be regrouped (the groupings differ in about 30 % of random elements): pass the operands in the order
+ * the model adds them.  a, b, c, sum_out: [rows, cols] of `dtype` with leading dimensions in elements; weight_g, bias_g: [cols] of the same dtype.
+ *   a and b both null:   no add (K1l2, the "dual norm": c is normalised as it is); sum_out must be null and both groups are required — one norm without an add is
+ *                        pq_layernorm_quant_rowwise, and asking for it here is PQ_ERR_BAD_ARG.  Exactly one of a, b null is PQ_ERR_BAD_ARG.
+ *   weight2 null:        one norm; bias2, q2, scale2 and h2 must be null as well.
+ * sum_out is required with the add and may be exactly one of a, b, c (same pointer and leading dimension); any other overlap of sum_out with an input, and any
+ * overlap of q1, scale1, h1, q2, scale2 or h2 with another operand, is PQ_ERR_BAD_ARG — as are a null operand (the biases and h1 / h2 excepted), ld < cols,
+ * cols >= 2^24, a negative or non-finite eps1 / eps2 and an unknown dtype — before any HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0:
+ * nothing is read or written, returns PQ_OK.  Row layouts and the PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time only, never bits). */
+int32_t pq_parallel_layernorm_quant_rowwise(const void* a, int64_t ld_a, const void* b, int64_t ld_b, const void* c, int64_t ld_c, void* sum_out, int64_t ld_s,
+                                            const void* weight1, const void* bias1, float eps1, const void* weight2, const void* bias2, float eps2, int32_t dtype,
+                                            int64_t rows, int64_t cols, int8_t* q1, int64_t ld_q1, float* scale1, void* h1, int64_t ld_h1, int8_t* q2, int64_t ld_q2,
+                                            float* scale2, void* h2, int64_t ld_h2, void* stream);
+
 /* K1u — K1 fused into the unary activation of a plain two-linear MLP (c_proj(act(c_fc(x)))): quantize(act(x)) per token in one pass.  x: [rows, cols] of `dtype`,
  * possibly a column block of a wider tensor (ld_x > cols).  Numerics, QSPEC U1-U4, binary32 throughout and ONE storage rounding of h:
  *   PQ_ACT_RELU       h = x < 0 ? +0 : x                        (a NaN and -0 pass: torch.relu, bit for bit)

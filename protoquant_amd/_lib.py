@@ -30,7 +30,7 @@ EXPORTS = (
     "pq_glu_quant_rowwise", "pq_selftest_glu_short",
     "pq_add_rmsnorm_quant_rowwise",
     "pq_layernorm_quant_rowwise", "pq_act_quant_rowwise",
-    "pq_add_layernorm_quant_rowwise",
+    "pq_add_layernorm_quant_rowwise", "pq_parallel_layernorm_quant_rowwise",
     "pq_gemma_rmsnorm_quant_rowwise", "pq_add_gemma_rmsnorm_quant_rowwise", "pq_gelu_mul_quant_rowwise",
     "pq_gemma_postnorm_add_rmsnorm_quant_rowwise",
 )
@@ -125,6 +125,9 @@ def lib() -> ctypes.CDLL:
     L.pq_layernorm_quant_rowwise.argtypes = [vp, i64, vp, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_add_layernorm_quant_rowwise.restype = i32
     L.pq_add_layernorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_parallel_layernorm_quant_rowwise.restype = i32
+    L.pq_parallel_layernorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, ctypes.c_float, vp, vp, ctypes.c_float, i32, i64, i64,
+                                                      vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp]
     L.pq_act_quant_rowwise.restype = i32
     L.pq_act_quant_rowwise.argtypes = [vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
     L.pq_gemma_rmsnorm_quant_rowwise.restype = i32

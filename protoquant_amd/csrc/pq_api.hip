@@ -9,6 +9,7 @@
 #include <mutex>
 #include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "gemm_epilogue.h"
 #include "pq_launch.h"
@@ -254,24 +255,26 @@ struct RowOperand {
 };
 const char kSumNote[] = " (the sum is the new residual stream: it is always stored)", kAffineNote[] = " (a LayerNorm without affine parameters is not supported)";
 
-// The checks of a row producer after its dtype (and kind), in this order: shape, eps (`eps` is null for a producer without a norm: no eps, no 2^24 bound on cols; `post_eps`: the second eps of K1pang, checked after it), the leading
+// The checks of a row producer after its dtype (and kind), in this order: shape, eps (`eps` is null for a producer without a norm: no eps, no 2^24 bound on cols; `post_eps`: the second eps of K1pang or K1pl / K1l2, checked after it and named `post_name`; at most 16 operands), the leading
 // dimensions in operand order, the empty problem (*empty: nothing to launch), the null pointers in operand order, then the overlaps.  An output may overlap neither an
 // input nor another output: the vector layouts load a clamped duplicate of a row's last vector into the slots past its end and the generic kernels read x again in every
 // pass, so an in-place h_out is not tolerated.  An in-out operand (sum_out) may BE a matrix input (same base and pitch: every element is read before it is written, by the
 // thread that writes it); any other overlap with an input is refused, and for the outputs it counts as the last of the inputs.
-int32_t check_row_producer(const char* fn, int64_t rows, int64_t cols, const float* eps, const RowOperand* ops, int n, bool* empty, const float* post_eps = nullptr) {
+int32_t check_row_producer(const char* fn, int64_t rows, int64_t cols, const float* eps, const RowOperand* ops, int n, bool* empty, const float* post_eps = nullptr,
+                           const char* post_name = "post_eps") {
     *empty = false;
     if (!eps && (rows < 0 || cols < 0)) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld)", fn, (long long)rows, (long long)cols);
     if (eps && (rows < 0 || cols < 0 || cols >= (1 << 24))) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (rows=%lld cols=%lld; cols < 2^24)", fn, (long long)rows, (long long)cols);
     if (eps && (!(*eps >= 0.0f) || *eps > 3.4028234e38f)) return fail(PQ_ERR_BAD_ARG, "%s: eps must be finite and >= 0 (eps=%g)", fn, (double)*eps);
-    if (post_eps && (!(*post_eps >= 0.0f) || *post_eps > 3.4028234e38f)) return fail(PQ_ERR_BAD_ARG, "%s: post_eps must be finite and >= 0 (post_eps=%g)", fn, (double)*post_eps);
+    if (post_eps && (!(*post_eps >= 0.0f) || *post_eps > 3.4028234e38f))
+        return fail(PQ_ERR_BAD_ARG, "%s: %s must be finite and >= 0 (%s=%g)", fn, post_name, post_name, (double)*post_eps);
     for (int i = 0; i < n; ++i)
         if (ops[i].ld_name && (ops[i].null_note || ops[i].p) && ops[i].ld < cols)
             return fail(PQ_ERR_BAD_ARG, "%s: %s %lld < cols %lld", fn, ops[i].ld_name, (long long)ops[i].ld, (long long)cols);
     if (rows == 0 || cols == 0) { *empty = true; return PQ_OK; }
     for (int i = 0; i < n; ++i)
         if (ops[i].null_note && !ops[i].p) return fail(PQ_ERR_BAD_ARG, "%s: %s is null%s", fn, ops[i].name, ops[i].null_note);
-    Extent e[8];
+    Extent e[16];
     for (int i = 0; i < n; ++i) e[i] = ops[i].ld_name ? extent_of(ops[i].p, ops[i].ld, rows, cols, ops[i].elem) : extent_of(ops[i].p, ops[i].ld, 1, ops[i].ld, ops[i].elem);
     for (int s = 0; s < n; ++s)
         for (int i = 0; i < n && ops[s].role == R_INOUT; ++i) {
@@ -279,7 +282,7 @@ int32_t check_row_producer(const char* fn, int64_t rows, int64_t cols, const flo
             if (!ops[i].ld_name) return fail(PQ_ERR_BAD_ARG, "%s: %s overlaps %s", fn, ops[s].name, ops[i].name);
             return fail(PQ_ERR_BAD_ARG, "%s: %s overlaps %s without being %s (same pointer and leading dimension)", fn, ops[s].name, ops[i].name, ops[i].name);
         }
-    int ins[8], nin = 0;      // what an output must stay clear of: the inputs, then the in-out operands, then the outputs after it
+    int ins[16], nin = 0;      // what an output must stay clear of: the inputs, then the in-out operands, then the outputs after it
     for (const Role r : {R_IN, R_INOUT})
         for (int i = 0; i < n; ++i)
             if (ops[i].role == r) ins[nin++] = i;
@@ -560,6 +563,56 @@ int32_t pq_add_layernorm_quant_rowwise(const void* x, int64_t ld_x, const void* 
     if (const int32_t rc = check_row_producer(fn, rows, cols, &eps, ops, 8, &empty); rc || empty) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::add_layernorm_quant_dispatch<dt>(x, ld_x, residual, ld_r, sum_out, ld_s, weight, bias, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
+    return check_launch(fn);
+}
+
+int32_t pq_parallel_layernorm_quant_rowwise(const void* a, int64_t ld_a, const void* b, int64_t ld_b, const void* c, int64_t ld_c, void* sum_out, int64_t ld_s,
+                                            const void* weight1, const void* bias1, float eps1, const void* weight2, const void* bias2, float eps2, int32_t dtype,
+                                            int64_t rows, int64_t cols, int8_t* q1, int64_t ld_q1, float* scale1, void* h1, int64_t ld_h1, int8_t* q2, int64_t ld_q2,
+                                            float* scale2, void* h2, int64_t ld_h2, void* stream) {
+    Range range_("pq:parallel_layernorm_quant (K1pl / K1l2)");
+    const char* fn = "pq_parallel_layernorm_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const bool add = a || b, two = weight2 != nullptr;
+    if (rows > 0 && cols > 0) {          // which of the three forms is asked for (an empty problem is a no-op whatever its pointers are)
+        if (!a != !b)
+            return fail(PQ_ERR_BAD_ARG, "%s: %s is null and %s is not (a and b go together: both null is the form without the add)", fn, a ? "b" : "a", a ? "a" : "b");
+        if (!add && sum_out) return fail(PQ_ERR_BAD_ARG, "%s: sum_out must be null without the add (a and b are null: nothing is summed or stored)", fn);
+        if (!two)
+            for (const auto& [name, p] : {std::pair<const char*, const void*>{"bias2", bias2}, {"q2", q2}, {"scale2", scale2}, {"h2", h2}})
+                if (p) return fail(PQ_ERR_BAD_ARG, "%s: %s must be null when weight2 is (one norm: the second group is absent as a whole)", fn, name);
+        if (!add && !two) return fail(PQ_ERR_BAD_ARG, "%s: neither an add (a, b null) nor a second norm (weight2 null): that is pq_layernorm_quant_rowwise", fn);
+    }
+    RowOperand ops[14];
+    int n = 0;
+    if (add) {
+        ops[n++] = {"a", a, R_IN, "ld_a", ld_a, eb, ""};
+        ops[n++] = {"b", b, R_IN, "ld_b", ld_b, eb, ""};
+    }
+    ops[n++] = {"c", c, R_IN, "ld_c", ld_c, eb, ""};
+    if (add) ops[n++] = {"sum_out", sum_out, R_INOUT, "ld_s", ld_s, eb, kSumNote};
+    ops[n++] = {"weight1", weight1, R_IN, nullptr, cols, eb, kAffineNote};
+    ops[n++] = {"bias1", bias1, R_IN, nullptr, cols, eb, nullptr};
+    if (two) {
+        ops[n++] = {"weight2", weight2, R_IN, nullptr, cols, eb, kAffineNote};
+        ops[n++] = {"bias2", bias2, R_IN, nullptr, cols, eb, nullptr};
+    }
+    ops[n++] = {"q1", q1, R_OUT, "ld_q1", ld_q1, 1, ""};
+    ops[n++] = {"scale1", scale1, R_OUT, nullptr, rows, 4, ""};
+    ops[n++] = {"h1", h1, R_OUT, "ld_h1", ld_h1, eb, nullptr};
+    if (two) {
+        ops[n++] = {"q2", q2, R_OUT, "ld_q2", ld_q2, 1, ""};
+        ops[n++] = {"scale2", scale2, R_OUT, nullptr, rows, 4, ""};
+        ops[n++] = {"h2", h2, R_OUT, "ld_h2", ld_h2, eb, nullptr};
+    }
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, &eps1, ops, n, &empty, two ? &eps2 : nullptr, "eps2"); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) {
+        pq::parallel_layernorm_quant_dispatch<dt>(a, ld_a, b, ld_b, c, ld_c, sum_out, ld_s, weight1, bias1, eps1, weight2, bias2, eps2, rows, cols, q1, ld_q1, scale1, h1, ld_h1,
+                                                  q2, ld_q2, scale2, h2, ld_h2, st);
+    });
     return check_launch(fn);
 }
 

@@ -35,6 +35,11 @@ template <int DT> void layernorm_quant_dispatch(const void* x, int64_t ldx, cons
                                                 float* scale, void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void add_layernorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, const void* bias,
                                                     float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
+// ---- parallel_layernorm_kernels.hip: the parallel residual (K1pl: a, b non-null; K1l2: a, b, sum_out null and both groups; wgt2 == nullptr: one norm, q2 / scale2 / h2 null)
+template <int DT> void parallel_layernorm_quant_dispatch(const void* a, int64_t lda, const void* b, int64_t ldb, const void* c, int64_t ldc, void* sum_out, int64_t lds,
+                                                         const void* wgt1, const void* bias1, float eps1, const void* wgt2, const void* bias2, float eps2, int64_t rows,
+                                                         int64_t cols, int8_t* q1, int64_t ldq1, float* scale1, void* h1, int64_t ldh1, int8_t* q2, int64_t ldq2,
+                                                         float* scale2, void* h2, int64_t ldh2, hipStream_t st);
 // ---- gemma_norm_kernels.hip, add_gemma_norm_kernels.hip, geglu_kernels.hip, gemma_postnorm_kernels.hip: the Gemma forms (K1ng, K1ang, K1gg, K1pang / K1pa)
 template <int DT> void gemma_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
                                                     void* h_out, int64_t ldh, hipStream_t st);

@@ -12,7 +12,11 @@ Pythia, and whatever else passes the same probes:
 the module objects untouched.  Composes with ``fuse_llama_layers`` (StarCoder2's q / k / v) in either call order.
 
 ``fuse_layernorm_residual(model)`` (opt-in, run after ``fuse_layernorm_layers``) also takes the two residual adds of a sequential pre-norm block into the LayerNorm that follows
-them (``add_layernorm_quantize``, kernel K1al: the residual stream is stored once and normalised from registers): see ``ResidualFusedBlock``."""
+them (``add_layernorm_quantize``, kernel K1al: the residual stream is stored once and normalised from registers): see ``ResidualFusedBlock``.
+
+``fuse_parallel_residual(model)`` (opt-in, an entry of its own, run after ``fuse_layernorm_layers``) does the same for the PARALLEL residual of GPT-NeoX / Pythia
+(``use_parallel_residual=True``) and Phi, which the entry above refuses by design: the three-way sum ``x + attn + mlp`` and the norm(s) of the next block run in one
+kernel (``add2_layernorm_quantize``, K1pl; the first block of a two-norm stack reads its input once, ``layernorm_quantize2``, K1l2): see ``ParallelFusedBlock``."""
 from __future__ import annotations
 
 import copy
@@ -23,9 +27,9 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .llama import _FusedSlice, _HandOver, _rf_clear_hook
+from .llama import _FusedSlice, _HandOver, _link_chain, _rf_clear_hook
 from .qlinear import FusedQLinear, qlinear
-from .qtensor import act_quantize, add_layernorm_quantize, layernorm_quantize
+from .qtensor import act_quantize, add2_layernorm_quantize, add_layernorm_quantize, layernorm_quantize, layernorm_quantize2
 
 
 class LayerNormQuant(nn.Module):
@@ -410,6 +414,19 @@ def residual_flow_plan(block: nn.Module, cls=None):
     norm_names = [n for n, m in block.named_children() if isinstance(m, LayerNormQuant)]
     if len(norm_names) != 2:
         return None
+    found = _probe_flow(block, cls, norm_names, _probe_block_once, lambda run: run.norm_out[0], lambda run: (run.norms, run.attn, run.mlp))
+    if found is None:
+        return None
+    run, run2, args, kwargs, forwards_extra, withheld, defaults, _ = found
+    return ResidualPlan(cls, run.norms[0], run.attn, run.norms[1], run.mlp, args, kwargs, forwards_extra, withheld, defaults, sorted(set(run.stateless) | set(run2.stateless)))
+
+
+def _probe_flow(block, cls, norm_names, probe_once, attn_input, roles):
+    """The part of a flow probe that does not depend on the flow: probe_once(block, cls, norm_names, given, poison=...) -> (run, the formula holds) is run with a
+    sentinel for every parameter of cls.forward (else with one parameter withheld, else with every parameter that has a default withheld), the attention call of that
+    run is recorded entry by entry — attn_input(run) is the tensor that stands in the norm output's place — and a second run with every default and a +Inf planted in
+    the attention's and the MLP's output must show the same roles(run) and the same call.  Returns (run, run2, args, kwargs, the block's **kwargs reach the attention,
+    withheld, defaults, the keyword arguments of the first run) or None."""
     try:
         ps = list(inspect.signature(cls.forward).parameters.values())[2:]          # (self, hidden_states, ...)
     except (TypeError, ValueError, AttributeError):
@@ -427,24 +444,25 @@ def residual_flow_plan(block: nn.Module, cls=None):
         if var_kw:
             given["pq_probe_extra"] = extra
         try:
-            run, ok = _probe_block_once(block, cls, norm_names, given)
+            run, ok = probe_once(block, cls, norm_names, given)
         except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
-            return None
-        return run if ok else None
+            return None, None
+        return (run, given) if ok else (None, None)
 
     # every parameter given; else one parameter withheld; else every parameter that has a default withheld
     tries = [()] + [(n,) for n in defaults] + [tuple(defaults)]
-    run, withheld = None, ()
+    run, given1 = None, None
     for withheld in tries:
-        run = attempt(withheld)
+        run, given1 = attempt(withheld)
         if run is not None:
             break
     if run is None:
         return None
     by_id = {id(s): n for n, s in sentinels.items()}
+    h1 = attn_input(run)
 
     def entry(v):
-        if v is run.norm_out[0]:
+        if v is h1:
             return _H
         if id(v) in by_id:
             return ("param", by_id[id(v)])
@@ -467,23 +485,24 @@ def residual_flow_plan(block: nn.Module, cls=None):
         return None
     # the same flow with every default (a parameter tested for truth must not change the stream): the recorded call must be the one made there too
     try:
-        run2, ok2 = _probe_block_once(block, cls, norm_names, {n: s for n, s in sentinels.items() if n not in defaults}, poison=True)
+        run2, ok2 = probe_once(block, cls, norm_names, {n: s for n, s in sentinels.items() if n not in defaults}, poison=True)
     except Exception:          # noqa: BLE001
         return None
-    if not ok2 or (run2.norms, run2.attn, run2.mlp) != (run.norms, run.attn, run.mlp):
+    if not ok2 or roles(run2) != roles(run):
         return None
     a2, kw2 = run2.attn_call
+    h2 = attn_input(run2)
 
     def same(e, v):
         if e == _H:
-            return v is run2.norm_out[0]
+            return v is h2
         if e[0] == "param":
             return v is (defaults[e[1]] if e[1] in defaults else sentinels[e[1]])
         return type(v) is type(e[1]) and v == e[1]
 
     if len(a2) != len(args) or set(kw2) != set(kwargs) or not all(same(e, v) for e, v in zip(args, a2)) or not all(same(kwargs[k], kw2[k]) for k in kwargs):
         return None
-    return ResidualPlan(cls, run.norms[0], run.attn, run.norms[1], run.mlp, args, kwargs, forwards_extra, withheld, defaults, sorted(set(run.stateless) | set(run2.stateless)))
+    return run, run2, args, kwargs, forwards_extra, withheld, defaults, given1
 
 
 class ResidualFusedBlock(nn.Module):
@@ -612,3 +631,257 @@ def fuse_layernorm_layers(model: nn.Module, fuse_norms: bool = True, fuse_act: b
                     did = True
         changed += int(did)
     return changed
+
+
+# ---------------------------------------------------------------- the parallel residual fused into the norm(s) of the next block (opt-in)
+_P24 = 16777216.0          # 2^24: in binary32, 2^24 + 1 rounds back to 2^24 — what tells the three groupings of a three-way sum apart
+
+
+def _assoc_operands():
+    """x, attention output, MLP output of the association run: the triple (2^24, -2^24, 1) rotated over three elements.  The three groupings of x + a + m give
+    three different vectors: (x + a) + m = [1, 0, 1], (a + m) + x = [1, 1, 0], (x + m) + a = [0, 1, 1] (per group of three elements)."""
+    t = torch.tensor([_P24, -_P24, 1.0])
+    rot = lambda k: torch.roll(t, k).repeat(4).reshape(1, 3, 4)          # noqa: E731
+    return {"x": rot(0), "a": rot(2), "m": rot(1)}
+
+
+def _rounding_operands():
+    """x, attention output, MLP output of the last run: seeded binary32 values of mixed magnitudes, on which every add rounds — a sum that only equals a grouping of
+    x + a + m in exact arithmetic (x / 2 + a + m + x / 2) does not give that grouping's bits here"""
+    g = torch.Generator().manual_seed(20)
+    return {k: torch.randn(1, 3, 4, generator=g) * torch.tensor([1.0, 37.0, 0.01, 1000.0]) for k in ("x", "a", "m")}
+
+
+_PAIRS = (("x", "a", "m"), ("a", "m", "x"), ("x", "m", "a"))          # (the pair added first, then the third operand)
+
+
+class ParallelPlan:
+    """What the probe of a block class's forward recorded (parallel_flow_plan): the attention and the MLP, the norm each of them reads (the same one in a block with
+    a single norm), `order` — the operands of the three-way sum ("x": the block's input, "a": the attention's output, "m": the MLP's) with the pair that the block
+    adds FIRST in front — and the replay of the attention call, the withheld parameters, the defaults and the stateless children as in ResidualPlan."""
+
+    def __init__(self, cls, attn, mlp, attn_norm, mlp_norm, order, args, kwargs, var_kw, withheld, defaults, stateless):
+        self.cls, self.attn, self.mlp, self.attn_norm, self.mlp_norm, self.order = cls, attn, mlp, attn_norm, mlp_norm, tuple(order)
+        self.norms = (attn_norm,) if attn_norm == mlp_norm else (attn_norm, mlp_norm)
+        self.args, self.kwargs, self.var_kw, self.withheld, self.defaults, self.stateless = tuple(args), dict(kwargs), var_kw, tuple(withheld), dict(defaults), tuple(stateless)
+        self.signature = inspect.signature(cls.forward)
+        ps = list(self.signature.parameters.values())
+        self.first = ps[1].name
+        self.var_kw_name = next((p.name for p in ps if p.kind == p.VAR_KEYWORD), None)
+
+
+class _ParallelRun:
+    """One run of a block forward for the parallel flow.  Every norm must be called once, WITH THE BLOCK'S INPUT ITSELF: the first one called returns 2 t, the second
+    t / 2 - 3.  A child that holds state and is called with a norm's output and nothing else is the MLP and returns h * h; called with a norm's output among other
+    arguments it is the attention and returns (h + 1, None).  Anything else is a refusal.  poison: as in _ProbeRun.  fixed: the association run — the attention and the
+    MLP return these tensors whatever they are called with."""
+
+    def __init__(self, norm_names, poison=False, fixed=None):
+        self.poison, self.fixed, self.x = poison, fixed, None
+        self.norm_names, self.norms, self.norm_out = set(norm_names), [], {}          # norms: names in call order; norm_out: name -> the tensor returned
+        self.attn, self.mlp, self.attn_call, self.attn_norm, self.mlp_norm, self.stateless = None, None, None, None, None, []
+
+    poisoned = _ProbeRun.poisoned
+
+    def child(self, name, v):
+        if name in self.norm_names:
+            def norm(t, _name=name):
+                if _name in self.norms or t is not self.x:
+                    raise _ProbeRefused(f"{_name} is called twice, or with something that is not the block's input")
+                self.norms.append(_name)
+                out = t * 2.0 if len(self.norms) == 1 else t * 0.5 - 3.0
+                self.norm_out[_name] = out
+                return out
+            return norm
+        if isinstance(v, (nn.ModuleList, nn.ModuleDict, nn.Sequential)):
+            raise _ProbeRefused(f"forward reads the container {name!r}")
+        if _stateless(v):
+            self.stateless.append(name)
+            return copy.deepcopy(v).eval()
+
+        def callee(*a, _name=name, **kw):
+            given = list(a) + list(kw.values())
+            hit = [n for n, o in self.norm_out.items() if any(g is o for g in given)]
+            if len(hit) != 1:
+                raise _ProbeRefused(f"{_name} is called with something that is not one norm's output")
+            h = self.norm_out[hit[0]]
+            if len(a) == 1 and not kw:
+                if self.mlp is not None:
+                    raise _ProbeRefused("a second child is called the way the MLP is")
+                self.mlp, self.mlp_norm = _name, hit[0]
+                return self.fixed["m"].clone() if self.fixed else self.poisoned(h * h, -1)
+            if self.attn is not None:
+                raise _ProbeRefused("a second child is called the way the attention is")
+            self.attn, self.attn_call, self.attn_norm = _name, (a, kw), hit[0]
+            return (self.fixed["a"].clone() if self.fixed else self.poisoned(h + 1.0, 0)), None
+        return callee
+
+    def roles(self):
+        return self.norms, self.attn, self.mlp, self.attn_norm, self.mlp_norm
+
+
+def _probe_parallel_once(block, cls, norm_names, given, poison=False, fixed=None):
+    """cls.forward on a stand-in with the keyword arguments `given`; (run, the formula holds) or raises.  With `fixed` the run records run.orders instead: the
+    groupings of the three-way sum that give the block's output bit for bit (not ok when none of the three does)."""
+    run = _ParallelRun(norm_names, poison, fixed)
+    x = fixed["x"].clone() if fixed else torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)          # small integers: every operation is exact
+    run.x = xin = x.clone()
+    with torch.no_grad(), torch.random.fork_rng(devices=[]):
+        out = cls.forward(_ProbeBlock(block, run), xin, **given)
+    if (not isinstance(out, torch.Tensor) or len(run.norms) != len(run.norm_names) or run.attn is None or run.mlp is None or out.shape != x.shape
+            or out.dtype != x.dtype or not torch.equal(xin, x)):          # (a forward that writes into its input is refused)
+        return run, False
+    if fixed:
+        run.orders = [o for o in _PAIRS if torch.equal(out, (fixed[o[0]] + fixed[o[1]]) + fixed[o[2]])]
+        return run, bool(run.orders)
+    ha, hm = run.norm_out[run.attn_norm], run.norm_out[run.mlp_norm]
+    want = (x + run.poisoned(ha + 1.0, 0)) + run.poisoned(hm * hm, -1)          # exact: every grouping gives these bits
+    return run, torch.equal(out, want)
+
+
+def _norm_is_hooked(m: nn.Module) -> bool:
+    return bool(m._forward_hooks or m._forward_pre_hooks)
+
+
+def parallel_flow_plan(block: nn.Module, cls=None):
+    """A ParallelPlan iff `cls.forward` (default: the block's own class) IS the parallel-residual data flow on this block:
+
+        out = x + A(N1(x), ...)[0] + M(N2(x))          (N2 may be N1: Phi)
+
+    with N1 (N2) the block's one or two LayerNormQuant children, each called once with the block's input itself, A the child called with a norm's output among other
+    arguments (it returns a tuple) and M the child called with a norm's output and nothing else, each called once; nothing else done to the stream (a child without
+    state — a dropout — may sit on it as long as the result still EQUALS the formula with that child in eval mode) and a tensor returned.  Probed, never matched by
+    name, with the machinery of residual_flow_plan: sentinels for the parameters, withheld parameters, a second run with every default and +Inf planted in both
+    outputs.  The ASSOCIATION of the three-way sum is probed as well — on exact small integers every grouping gives the same bits, so one more run has the attention
+    and the MLP return values that tell the groupings apart in binary32 (_assoc_operands), and a last one values on which every add rounds (_rounding_operands); the
+    plan records which pair is added first, and a flow that does not give the bits of one and the same grouping in both runs is refused.  None for everything else: a sequential residual, a scaled sum, a norm applied to anything but the input, a block that returns a
+    tuple, a norm that carries a forward or forward-pre hook (the fused block reads the norm's parameters and no longer calls it)."""
+    cls = cls or type(block)
+    norms = {n: m for n, m in block.named_children() if isinstance(m, LayerNormQuant)}
+    if len(norms) not in (1, 2) or any(_norm_is_hooked(m) for m in norms.values()):
+        return None
+    found = _probe_flow(block, cls, list(norms), _probe_parallel_once, lambda run: run.norm_out[run.attn_norm], _ParallelRun.roles)
+    if found is None:
+        return None
+    run, run2, args, kwargs, forwards_extra, withheld, defaults, given = found
+    try:
+        run3, ok3 = _probe_parallel_once(block, cls, list(norms), given, fixed=_assoc_operands())
+    except Exception:          # noqa: BLE001
+        return None
+    if not ok3 or run3.roles() != run.roles() or len(run3.orders) != 1:
+        return None
+    try:          # the grouping found must also be what the block computes where every add rounds
+        run4, ok4 = _probe_parallel_once(block, cls, list(norms), given, fixed=_rounding_operands())
+    except Exception:          # noqa: BLE001
+        return None
+    if not ok4 or run4.roles() != run.roles() or run3.orders[0] not in run4.orders:
+        return None
+    stateless = sorted(set(run.stateless) | set(run2.stateless) | set(run3.stateless) | set(run4.stateless))
+    return ParallelPlan(cls, run.attn, run.mlp, run.attn_norm, run.mlp_norm, run3.orders[0], args, kwargs, forwards_extra, withheld, defaults, stateless)
+
+
+class ParallelFusedBlock(nn.Module):
+    """A parallel-residual decoder block (GPT-NeoX with use_parallel_residual, Phi) whose three-way sum runs inside the LayerNorm + quantisation kernel of the NEXT
+    block (K1pl, add2_layernorm_quantize):
+
+        ha, hm     = the QTensors handed over for this very tensor, else N1 and N2 of hidden in one launch (K1l2, layernorm_quantize2; one norm: K1l)
+        attn_out   = A(...)[0], called the way the block's own forward calls it (ParallelPlan), with ha in the norm output's place
+        m          = M(hm)
+        last of the chain:  return the two torch adds, in the association the probe recorded
+        otherwise:          q1[, q2], out = add2_layernorm_quantize(the three operands in that association, the NEXT block's norm parameters);
+                            hand the QTensor(s) to the next block;  return out
+
+    What the block returns is the real summed tensor (the bits of the two torch adds in the block's own association: QSPEC A2), so hooks, output_hidden_states and
+    the final norm see what they saw.  The norm modules stay the model's, object for object, but are no longer called: only weight / bias / eps are read (which is why
+    a block whose norm carries a hook is not converted).  Installed like ResidualFusedBlock — a run-time class deriving from this one and from the original class —
+    with the same hand-over discipline and the same fallbacks to the original forward."""
+    _pq_parallel_fused = True
+
+    def forward(self, *args, **kwargs):
+        plan = self._pfb_plan
+        bound = plan.signature.bind(self, *args, **kwargs)          # (a TypeError here is the one the original forward would raise)
+        bound.apply_defaults()
+        given = bound.arguments
+        extras = given.get(plan.var_kw_name, {}) if plan.var_kw_name else {}
+        hidden = given[plan.first]
+        if ((self.training and plan.stateless) or not isinstance(hidden, torch.Tensor) or (extras and not plan.var_kw)
+                or any(given[n] is not plan.defaults[n] for n in plan.withheld)):
+            self._rf_inbox.clear()
+            return plan.cls.forward(self, *args, **kwargs)
+        handed = self._rf_inbox.take(hidden)
+        if handed is not None:
+            ha, hm = handed
+        elif len(plan.norms) == 1:
+            n1 = getattr(self, plan.attn_norm)
+            ha = hm = layernorm_quantize(hidden, n1.weight, n1.bias, n1.eps)
+        else:
+            n1, n2 = getattr(self, plan.attn_norm), getattr(self, plan.mlp_norm)
+            ha, hm = layernorm_quantize2(hidden, n1.weight, n1.bias, n2.weight, n2.bias, n1.eps, n2.eps)
+        value = lambda e: ha if e == _H else given[e[1]] if e[0] == "param" else e[1]          # noqa: E731
+        attn_out = getattr(self, plan.attn)(*(value(e) for e in plan.args), **{k: value(e) for k, e in plan.kwargs.items()}, **extras)[0]
+        m = getattr(self, plan.mlp)(hm)
+        operand = {"x": hidden, "a": attn_out, "m": m}
+        p, q, r = (operand[k] for k in plan.order)
+        nxt = self._rf_next[0]
+        if nxt is None:
+            return (p + q) + r
+        np_ = nxt._pfb_plan
+        n1 = getattr(nxt, np_.attn_norm)
+        if len(np_.norms) == 1:
+            q1, out = add2_layernorm_quantize(p, q, r, n1.weight, n1.bias, n1.eps)
+            q2 = q1
+        else:
+            n2 = getattr(nxt, np_.mlp_norm)
+            q1, q2, out = add2_layernorm_quantize(p, q, r, n1.weight, n1.bias, n1.eps, n2.weight, n2.bias, n2.eps)
+        nxt._rf_inbox.put(out, (q1, q2))
+        return out
+
+    def __reduce_ex__(self, protocol):          # (the class is made at run time: a copy — deep or pickled — makes it again from the original class)
+        return _rebuild_parallel_block, (self._pfb_plan.cls,), self.__dict__
+
+
+_PFB_CLASSES: dict = {}
+
+
+def _parallel_fused_block_class(cls):
+    if cls not in _PFB_CLASSES:
+        _PFB_CLASSES[cls] = type("ParallelFused" + cls.__name__, (ParallelFusedBlock, cls), {"__doc__": ParallelFusedBlock.__doc__})
+    return _PFB_CLASSES[cls]
+
+
+def _rebuild_parallel_block(cls):
+    fused = _parallel_fused_block_class(cls)
+    return fused.__new__(fused)
+
+
+def fuse_parallel_residual(model: nn.Module) -> int:
+    """Opt-in, after fuse_layernorm_layers (which it leaves exactly as it was, as it does fuse_layernorm_residual: an entry of its own): every block of a ModuleList
+    that has one or two LayerNormQuant children and whose class's forward passes parallel_flow_plan becomes a ParallelFusedBlock (in place).  A refused block keeps
+    the fusions it has and breaks the chain (its predecessor ends with the two torch adds); the model's final norm is not touched.  The module that owns the
+    ModuleList gets the always-called forward hook that drops every pending hand-over when its forward ends.  Returns the number of blocks changed by THIS call (a
+    second call finds nothing left to change); parallel_fused_blocks(model) counts them over all calls.  Families whose norms fuse_layernorm_layers does not turn into
+    LayerNormQuant (GPT-J, Falcon, Cohere) have nothing to probe: 0, every module object left alone."""
+    n = 0
+    for owner in list(model.modules()):
+        for _, stack in list(owner.named_children()):
+            if not isinstance(stack, nn.ModuleList):
+                continue
+            fresh = []
+            for block in stack:
+                if getattr(type(block), "_pq_parallel_fused", False) or getattr(type(block), "_pq_residual_fused", False):
+                    continue
+                plan = parallel_flow_plan(block)
+                if plan is None:
+                    continue
+                block._pfb_plan = plan
+                block._rf_inbox, block._rf_next = _HandOver(), [None]
+                block.__class__ = _parallel_fused_block_class(plan.cls)
+                fresh.append(block)
+            _link_chain(owner, stack, fresh, ParallelFusedBlock)
+            n += len(fresh)
+    return n
+
+
+def parallel_fused_blocks(model: nn.Module) -> int:
+    """the number of ParallelFusedBlock modules in `model` (what fuse_parallel_residual made, over all calls)"""
+    return sum(1 for m in model.modules() if isinstance(m, ParallelFusedBlock))

@@ -368,6 +368,114 @@ def add_layernorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torc
     return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
 
 
+def _check_ln_group(what: str, x: torch.Tensor, weight, bias, suffix: str = ""):
+    """the affine parameters of one LayerNorm group against the rows they normalise (the messages of layernorm_quantize)"""
+    if weight is None:
+        raise ValueError(f"{what}: weight{suffix} is None — a LayerNorm without affine parameters (elementwise_affine=False) is not supported")
+    L.require_gpu(weight, f"{what}(weight{suffix})")
+    if weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} needs a weight{suffix} of shape ({x.shape[-1]},) and the same dtype/device, "
+                         f"got {tuple(weight.shape)} {weight.dtype}")
+    if bias is not None:
+        L.require_gpu(bias, f"{what}(bias{suffix})")
+        if bias.shape != weight.shape or bias.dtype != x.dtype or bias.device != x.device:
+            raise ValueError(f"{what}: bias{suffix} {tuple(bias.shape)} {bias.dtype} must match the weight{suffix} {tuple(weight.shape)} {weight.dtype}")
+
+
+def _parallel_launch(what: str, a2, b2, c2, s2, groups, return_h: bool, like: torch.Tensor):
+    """One launch of pq_parallel_layernorm_quant_rowwise on 2-D row views (a2, b2, s2 None: no add); groups: one or two (weight, bias, eps).  Returns per group
+    (QTensor, h or None)."""
+    rows, cols = c2.shape
+    code = L.dtype_code(c2.dtype)
+    dev = c2.device
+    ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
+    ldo = lambda t: L.ld(t) if t is not None else 0                  # noqa: E731
+    outs, args = [], []
+    for g in (0, 1):
+        if g < len(groups):
+            w, b, eps = groups[g]
+            w = w.contiguous()
+            b = b.contiguous() if b is not None else None
+            q = torch.empty((rows, cols), dtype=torch.int8, device=dev)
+            scale = torch.empty((rows,), dtype=torch.float32, device=dev)
+            h = torch.empty((rows, cols), dtype=c2.dtype, device=dev) if return_h else None
+            outs.append((q, scale, h))
+            args.append((w, b, float(eps)))
+        else:
+            outs.append((None, None, None))
+            args.append((None, None, 0.0))
+    with torch.cuda.device(dev):
+        L.check(L.lib().pq_parallel_layernorm_quant_rowwise(
+            ptr(a2), ldo(a2), ptr(b2), ldo(b2), c2.data_ptr(), L.ld(c2), ptr(s2), ldo(s2),
+            ptr(args[0][0]), ptr(args[0][1]), args[0][2], ptr(args[1][0]), ptr(args[1][1]), args[1][2], code, rows, cols,
+            ptr(outs[0][0]), cols, ptr(outs[0][1]), ptr(outs[0][2]), cols, ptr(outs[1][0]), cols if outs[1][0] is not None else 0, ptr(outs[1][1]), ptr(outs[1][2]),
+            cols if outs[1][2] is not None else 0, L.stream_ptr(c2)), what)
+    return [(QTensor(q.reshape(like.shape), scale, 1, like.dtype, like.shape), h.reshape(like.shape) if h is not None else None) for q, scale, h in outs[:len(groups)]]
+
+
+def add2_layernorm_quantize(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, eps: float = 1e-5,
+                            weight2: torch.Tensor | None = None, bias2: torch.Tensor | None = None, eps2: float | None = None, out: torch.Tensor | None = None,
+                            return_h: bool = False):
+    """summed = (a + b) + c — two adds in THIS association, each rounded to the storage dtype (QSPEC A2) — then layernorm_quantize(summed, weight, bias, eps) and, with
+    `weight2`, layernorm_quantize(summed, weight2, bias2, eps2) as well, in ONE kernel (K1pl): the parallel residual of a GPT-NeoX / Phi block and the norm(s) of the next
+    block.  The sum is stored once; its mean and variance are computed once and serve both norms.  Returns (QTensor, summed) or (QTensor, QTensor2, summed), with h (and
+    h2) appended under return_h=True; every one of them holds the bits of the two torch adds followed by layernorm_quantize(..., return_h=True) per norm.  Addition
+    commutes, so a and b may be swapped, but the three may not be regrouped: pass them in the order the model adds them.  a, b and c have the same shape, dtype and
+    device; the biases may be None; eps2 defaults to eps.  `out` (optional, the same shape and dtype) receives the sum and may be a, b or c themselves; any other tensor
+    that overlaps an input is refused.  `summed` has a's shape."""
+    what = "add2_layernorm_quantize"
+    for name, t in (("a", a), ("b", b), ("c", c)):
+        L.require_gpu(t, f"{what}({name})")
+    for name, t in (("b", b), ("c", c)):
+        if a.dim() < 1 or a.shape != t.shape or a.dtype != t.dtype or a.device != t.device:
+            raise ValueError(f"{what}: a {tuple(a.shape)} {a.dtype} {a.device} and {name} {tuple(t.shape)} {t.dtype} {t.device} must match")
+    _check_ln_group(what, a, weight, bias)
+    two = weight2 is not None
+    if two:
+        _check_ln_group(what, a, weight2, bias2, "2")
+    elif bias2 is not None or eps2 is not None:
+        raise ValueError(f"{what}: bias2 / eps2 are given without weight2 (the second norm is absent as a whole)")
+    if out is not None:
+        L.require_gpu(out, f"{what}(out)")
+        if out.shape != a.shape or out.dtype != a.dtype or out.device != a.device:
+            raise ValueError(f"{what}: out {tuple(out.shape)} {out.dtype} must have a's shape {tuple(a.shape)} and dtype {a.dtype}")
+    eps2 = eps if eps2 is None else eps2
+    L.dtype_code(a.dtype)
+    a2, b2, c2 = _rows_view(a), _rows_view(b), _rows_view(c)
+    rows, cols = a2.shape
+    summed = torch.empty(a.shape, dtype=a.dtype, device=a.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, what)
+    if rows == 0 or cols == 0:          # nothing to add: the empty sum through K1l (scales of empty rows are 1, QSPEC Q3)
+        res = [layernorm_quantize(summed, w, bi, e, True) for w, bi, e in ([(weight, bias, eps)] + ([(weight2, bias2, eps2)] if two else []))]
+    else:
+        res = _parallel_launch(what, a2, b2, c2, s2, [(weight, bias, eps)] + ([(weight2, bias2, eps2)] if two else []), return_h, a)
+    ret = tuple(r[0] for r in res) + (summed,)
+    return ret + tuple(r[1] for r in res) if return_h else ret
+
+
+def layernorm_quantize2(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, weight2: torch.Tensor, bias2: torch.Tensor | None, eps: float = 1e-5,
+                        eps2: float | None = None, return_h: bool = False):
+    """layernorm_quantize(x, weight, bias, eps) and layernorm_quantize(x, weight2, bias2, eps2) in ONE kernel (K1l2, the "dual norm" of the first block of a GPT-NeoX
+    stack with a parallel residual): x is read once, its mean and variance are computed once and each norm applies its own eps, affine map and quantisation.  Returns
+    (QTensor, QTensor2) or (QTensor, QTensor2, h, h2) with return_h=True, the bits of the two separate calls.  The biases may be None; eps2 defaults to eps."""
+    what = "layernorm_quantize2"
+    L.require_gpu(x, f"{what}(x)")
+    if x.dim() < 1:
+        raise ValueError(f"{what}: x needs at least 1 dimension")
+    _check_ln_group(what, x, weight, bias)
+    _check_ln_group(what, x, weight2, bias2, "2")
+    eps2 = eps if eps2 is None else eps2
+    L.dtype_code(x.dtype)
+    x2 = _rows_view(x)
+    rows, cols = x2.shape
+    if rows == 0 or cols == 0:
+        res = [layernorm_quantize(x, w, bi, e, True) for w, bi, e in ((weight, bias, eps), (weight2, bias2, eps2))]
+    else:
+        res = _parallel_launch(what, None, None, x2, None, [(weight, bias, eps), (weight2, bias2, eps2)], return_h, x)
+    ret = tuple(r[0] for r in res)
+    return ret + tuple(r[1] for r in res) if return_h else ret
+
+
 def act_quantize(x: torch.Tensor, kind: str, return_h: bool = False):
     """quantize(act(x), axis=-1) in ONE pass (kernel K1u) for the unary activation of a plain two-linear MLP: kind "relu" (torch.relu), "gelu_tanh" (gelu_new,
     gelu_pytorch_tanh) or "gelu_erf" (F.gelu's default).  x may be a column slice of a wider tensor.  Numerics: QSPEC U1-U4 then Q1-Q6 — relu holds torch's bits;
