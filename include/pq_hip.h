@@ -86,7 +86,8 @@ int32_t pq_silu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, in
  *   kind PQ_GLU_CLAMPED_SILU  (DeepSeek-V4's experts):  h = silu(min(g, L)) * clamp(u, -L, +L)
  *   kind PQ_GLU_ALPHA_SIGMOID (GPT-OSS's experts):      gc = min(g, L);  h = (clamp(u, -L, +L) + 1) * (gc * sigmoid(alpha * gc))
  * with a storage rounding after every step a chain of tensor ops would round at; a NaN in g or u propagates, then Q1-Q6 on the rows of h.  Layouts and argument
- * meaning as pq_silu_mul_quant_rowwise (g, u: the two column halves of one [rows, 2 cols] tensor qualify, ld = 2 cols; h_out nullable).  limit must be finite, > 0
+ * meaning as pq_silu_mul_quant_rowwise (PQ_SILU_TPR included: time only, never bits; g, u: the two column halves of one [rows, 2 cols] tensor qualify, ld = 2 cols;
+ * h_out nullable).  limit must be finite, > 0
  * and must not round to zero in `dtype`; alpha must be finite (it is not read for PQ_GLU_CLAMPED_SILU).  A bad kind / dtype / limit / alpha is PQ_ERR_BAD_ARG before
  * any HIP call; rows == 0 or cols == 0 is a no-op. */
 #define PQ_GLU_CLAMPED_SILU 0

@@ -2,14 +2,13 @@
 //   kind 0, CLAMPED_SILU   (DeepSeek-V4):  h = silu(min(g, L)) * clamp(u, -L, +L)
 //   kind 1, ALPHA_SIGMOID  (GPT-OSS):      h = (clamp(u, -L, +L) + 1) * gc * sigmoid(alpha * gc),  gc = min(g, L)
 //   -> per-token int8 codes + row scales (the `down` input of the experts), without the 16-bit activation ever going to HBM.
-// The skeleton is silu_mul_quant_vec's (producer_kernels.hip): TPR threads own a row, every 16-byte load is issued before the first use, the row of h lives in
-// registers between the amax reduction and the encode.  The device helpers are CALLED from producer_device.h; the kernels here are templates of their own in an
-// object file of their own, so the register allocation of K1s / K1n does not depend on this file.
+// The kernels and the layout decision are the activation family's (rowmap_kernels.h), the exponential and the quotient producer_device.h's; this file holds the
+// op's arithmetic, its trait, the self-test kernel, the host helpers and the instantiations, in an object file of its own.
 // Algorithmic traffic: read 2 x elem bytes, write 1 B/elem + 4 B/row (+ elem bytes when h is also requested).
 #include <cmath>
 #include <cstring>
 
-#include "producer_device.h"
+#include "rowmap_kernels.h"
 #include "pq_launch.h"
 
 namespace pq {
@@ -30,7 +29,7 @@ template <int DT> __device__ __forceinline__ v2f store_round(v2f x) {          /
 //    correctly rounded sequence (rcp, one Newton step, the quotient and two residual corrections) without the operand scaling, which is only needed when an
 //    intermediate can overflow or lose bits to underflow.  For |a| <= 86 none can: d lies in [1, 2^125), 1 / d in (2^-125, 1], the residuals 1 - d q are exact.
 //    A zero needs no exception here (d = 2, every step exact; the sign of a -0 gate comes from gc in gc * s).  Waves holding an |a| that may exceed 86, an Inf or
-//    a NaN take the `/` path (glu_fast_ok, decided once per wave on the raw bits of g).  pq_selftest_glu_short runs every 16-bit pattern through both.
+//    a NaN take the `/` path (GluOp::fast_ok, decided once per wave on the raw bits of g).  pq_selftest_glu_short runs every 16-bit pattern through both.
 template <int DT, int KIND, bool FASTDIV, int NP>
 __device__ __forceinline__ void glu_stage(const v2f (&g)[NP], const v2f (&u)[NP], float L, float alpha, v2f (&h)[NP]) {
     v2f gc[NP], uc[NP];
@@ -42,46 +41,18 @@ __device__ __forceinline__ void glu_stage(const v2f (&g)[NP], const v2f (&u)[NP]
     if constexpr (KIND == GLU_CLAMPED_SILU) {
         silu_mul_stage<DT, FASTDIV, NP, FASTDIV && DT != PQ_F32>(gc, uc, h);
     } else {
-        v2f a[NP], tc[NP], n[NP], r[NP], p[NP], d[NP], s[NP], glu[NP], v[NP];
+        v2f a[NP], na[NP], d[NP], s[NP], glu[NP], v[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) a[k] = store_round<DT>(gc[k] * splat(alpha));                                      // G2
-        // G3: 1 + exp_spec(-a), QSPEC S1-S4 as in silu_mul_stage (the clamp is a med3 again: a NaN a is a NaN gc, put back below)
+        // G3: 1 + exp_spec(-a) (the clamp is a med3 again: a NaN a is a NaN gc, put back below)
 #pragma unroll
-        for (int k = 0; k < NP; ++k) tc[k] = v2f{__builtin_amdgcn_fmed3f(-a[k].x, -30.0f, 100.0f), __builtin_amdgcn_fmed3f(-a[k].y, -30.0f, 100.0f)};
-#pragma unroll
-        for (int k = 0; k < NP; ++k) n[k] = tc[k] * splat(__builtin_bit_cast(float, 0x3FB8AA3Bu));
-#pragma unroll
-        for (int k = 0; k < NP; ++k) n[k] = v2f{__builtin_rintf(n[k].x), __builtin_rintf(n[k].y)};
-#pragma unroll
-        for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-__builtin_bit_cast(float, 0x3F317200u)), tc[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-__builtin_bit_cast(float, 0x35BFBE8Eu)), r[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) p[k] = pk_fma(splat(__builtin_bit_cast(float, 0x39500D01u)), r[k], splat(__builtin_bit_cast(float, 0x3AB60B61u)));
-        constexpr uint32_t kC[6] = {0x3C088889u, 0x3D2AAAABu, 0x3E2AAAABu, 0x3F000000u, 0x3F800000u, 0x3F800000u};
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-#pragma unroll
-            for (int k = 0; k < NP; ++k) p[k] = pk_fma(p[k], r[k], splat(__builtin_bit_cast(float, kC[c])));
-        }
-#pragma unroll
-        for (int k = 0; k < NP; ++k) d[k] = splat(1.0f) + v2f{__builtin_ldexpf(p[k].x, (int)n[k].x), __builtin_ldexpf(p[k].y, (int)n[k].y)};
+        for (int k = 0; k < NP; ++k) na[k] = v2f{-a[k].x, -a[k].y};
+        exp_spec_stage<NP, true, true>(na, d);
         if constexpr (FASTDIV) {
-            v2f y0[NP], y[NP], q[NP], e[NP];
+            v2f one[NP];
 #pragma unroll
-            for (int k = 0; k < NP; ++k) y0[k] = v2f{__builtin_amdgcn_rcpf(d[k].x), __builtin_amdgcn_rcpf(d[k].y)};
-#pragma unroll
-            for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], y0[k], splat(1.0f));
-#pragma unroll
-            for (int k = 0; k < NP; ++k) y[k] = pk_fma(e[k], y0[k], y0[k]);
-#pragma unroll
-            for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], y[k], splat(1.0f));          // (the quotient 1 * y is y)
-#pragma unroll
-            for (int k = 0; k < NP; ++k) q[k] = pk_fma(e[k], y[k], y[k]);
-#pragma unroll
-            for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], q[k], splat(1.0f));
-#pragma unroll
-            for (int k = 0; k < NP; ++k) s[k] = pk_fma(e[k], y[k], q[k]);
+            for (int k = 0; k < NP; ++k) one[k] = splat(1.0f);
+            fast_div_stage<NP>(one, d, s);
         } else {
 #pragma unroll
             for (int k = 0; k < NP; ++k) s[k] = v2f{1.0f / d[k].x, 1.0f / d[k].y};
@@ -99,139 +70,38 @@ __device__ __forceinline__ void glu_stage(const v2f (&g)[NP], const v2f (&u)[NP]
 #pragma unroll
     for (int k = 0; k < NP; ++k) h[k] = v2f{__builtin_isunordered(g[k].x, u[k].x) ? qnan : h[k].x, __builtin_isunordered(g[k].y, u[k].y) ? qnan : h[k].y};
 }
-template <int DT, int KIND>
-__device__ __forceinline__ float glu_spec(float g, float u, float L, float alpha) {
-    const v2f ga[1] = {v2f{g, g}}, ua[1] = {v2f{u, u}};
-    v2f h[1];
-    glu_stage<DT, KIND, false, 1>(ga, ua, L, alpha, h);
-    return h[0].x;
-}
-
 // The fast-division test on the min / max of the |g| bit patterns of a wave (vec_absminmax_bits).  |gc| <= |g| (the clamp only lowers a positive gate), so a
 // bound on |g| bounds what the division sees.  CLAMPED_SILU: silu_fast_div_ok as it is (0 < |g| <= 86).  ALPHA_SIGMOID: |g| <= gmax, the largest storage value
 // with gmax |alpha| <= 86 and gmax <= 86 (computed on the host, rounded DOWN: 86 is a value of every storage dtype and rounding is monotone, so |a| <= 86).
-template <int DT, int KIND> __device__ __forceinline__ bool glu_fast_ok(uint32_t mn, uint32_t mx, uint32_t gmax_bits) {
-    if constexpr (KIND == GLU_CLAMPED_SILU) return silu_fast_div_ok<DT>(mn, mx);
-    else return mx <= gmax_bits;
-}
-
-// one 16-byte vector of g and of u -> one 16-byte vector of h in the storage dtype
-template <int DT, int KIND, bool FASTDIV>
-__device__ __forceinline__ v4u glu_vec(const v4u& gv, const v4u& uv, float L, float alpha) {
-    constexpr int NP = DT == PQ_F32 ? 2 : 4;
-    v2f g[NP], u[NP], h[NP];
-    v4u out;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        if constexpr (DT == PQ_F32) {
-            const uint32_t g0 = gv[2 * j], g1 = gv[2 * j + 1], u0 = uv[2 * j], u1 = uv[2 * j + 1];   // copies first (hipcc quirk, as silu_mul_vec)
-            g[j] = v2f{__builtin_bit_cast(float, g0), __builtin_bit_cast(float, g1)};
-            u[j] = v2f{__builtin_bit_cast(float, u0), __builtin_bit_cast(float, u1)};
-        } else {
-            const uint32_t gw = gv[j], uw = uv[j];
-            g[j] = Pair<DT>::unpack(gw);
-            u[j] = Pair<DT>::unpack(uw);
-        }
+template <int KIND>
+struct GluOp {
+    static constexpr int kInputs = 2;
+    static constexpr bool kFastSplit = true, kWideRows = true, kSplitModes = false;
+    struct Params { float L, alpha; uint32_t gmax_bits; };
+    template <int DT> __device__ static __forceinline__ bool fast_ok(uint32_t mn, uint32_t mx, const Params& p) {
+        if constexpr (KIND == GLU_CLAMPED_SILU) return silu_fast_div_ok<DT>(mn, mx);
+        else return mx <= p.gmax_bits;
     }
-    glu_stage<DT, KIND, FASTDIV, NP>(g, u, L, alpha, h);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        if constexpr (DT == PQ_F32) {
-            const float hx = h[j].x, hy = h[j].y;
-            out[2 * j] = __builtin_bit_cast(uint32_t, hx);
-            out[2 * j + 1] = __builtin_bit_cast(uint32_t, hy);
-        } else {
-            out[j] = Pair<DT>::pack(h[j]);
-        }
+    template <int DT, bool FASTDIV> __device__ static __forceinline__ v4u vec(const v4u& gv, const v4u& uv, const Params& p) {
+        return map_vec<DT>(gv, uv, [&](const auto& g, const auto& u, auto& h) { glu_stage<DT, KIND, FASTDIV, DT == PQ_F32 ? 2 : 4>(g, u, p.L, p.alpha, h); });
     }
-    return out;
-}
-
-template <int DT, int KIND, int VPT, int TPR, bool WRITE_H>
-__global__ __launch_bounds__(TPR > 256 ? TPR : 256) void glu_quant_vec(const uint8_t* __restrict__ g, int64_t ldg_bytes, const uint8_t* __restrict__ u,
-                                                                       int64_t ldu_bytes, int64_t rows, int nvec, float L, float alpha, uint32_t gmax_bits,
-                                                                       int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale,
-                                                                       uint8_t* __restrict__ h_out, int64_t ldh_bytes) {
-    constexpr int BS = TPR > 256 ? TPR : 256;
-    constexpr int RPB = BS / TPR;
-    const int t = threadIdx.x % TPR;
-    int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / TPR;
-    const bool active = row < rows;
-    row = active ? row : rows - 1;
-    const uint8_t* gr = g + row * ldg_bytes;
-    const uint8_t* ur = u + row * ldu_bytes;
-
-    // every load is issued before the first use (clamped addresses: a duplicate of the tail vector changes no max)
-    v4u gv[VPT], uv[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = i * TPR + t;
-        const int64_t off = (int64_t)(idx < nvec ? idx : nvec - 1) * 16;
-        gv[i] = *reinterpret_cast<const v4u*>(gr + off);
-        uv[i] = *reinterpret_cast<const v4u*>(ur + off);
+    template <int DT> __device__ static __forceinline__ float spec(float g, float u, const Params& p) {
+        return map_one(g, u, [&](const auto& ga, const auto& ua, auto& h) { glu_stage<DT, KIND, false, 1>(ga, ua, p.L, p.alpha, h); });
     }
-    v4u hv[VPT];
-    uint32_t ab = 0;
-    uint32_t gmn = 0xFFFFFFFFu, gmx = 0u;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) vec_absminmax_bits<DT>(gv[i], gmn, gmx);
-    const bool fast_div = __builtin_amdgcn_ballot_w64(!glu_fast_ok<DT, KIND>(gmn, gmx, gmax_bits)) == 0ull;   // wave-uniform
-    auto produce = [&](auto fast) {
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int idx = i * TPR + t;
-            // slots past the row's end (whole waves of them when the width is not VPT * TPR vectors) skip the arithmetic
-            hv[i] = idx < nvec ? glu_vec<DT, KIND, decltype(fast)::value>(gv[i], uv[i], L, alpha) : v4u{0u, 0u, 0u, 0u};
-            ab = vec_amax_bits<DT>(hv[i], ab);
-            if constexpr (WRITE_H) {
-                if (active && idx < nvec) store_wt_b128(h_out + row * ldh_bytes + (int64_t)idx * 16, hv[i]);
-            }
-        }
-    };
-    if (fast_div) produce(std::true_type{});
-    else produce(std::false_type{});
-    reduce_and_encode<DT, VPT, TPR>(hv, ab, t, nvec, active, row, q, ldq, scale);
-}
+};
 
-// generic path: any cols / leading dimensions / alignment.  One block per row; h is recomputed in the second pass (the specified sequence, with `/`).
-template <int DT, int KIND>
-__global__ __launch_bounds__(256) void glu_quant_generic(const void* __restrict__ g, int64_t ldg, const void* __restrict__ u, int64_t ldu, int64_t cols,
-                                                         float L, float alpha, int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale,
-                                                         void* __restrict__ h_out, int64_t ldh) {
-    using S = typename Elem<DT>::store_t;
-    const int64_t row = blockIdx.x;
-    const S* gr = reinterpret_cast<const S*>(g) + row * ldg;
-    const S* ur = reinterpret_cast<const S*>(u) + row * ldu;
-    auto h_at = [&](int64_t c) -> S { return Elem<DT>::from_f32(glu_spec<DT, KIND>(Elem<DT>::to_f32(gr[c]), Elem<DT>::to_f32(ur[c]), L, alpha)); };
-    float amax = 0.0f;
-    for (int64_t c = threadIdx.x; c < cols; c += 256) {
-        const S h = h_at(c);
-        if (h_out) reinterpret_cast<S*>(h_out)[row * ldh + c] = h;
-        amax = amax_step(amax, Elem<DT>::to_f32(h));
-    }
-    amax = wave_max(amax);
-    __shared__ float part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = amax;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 4; ++w) amax = amax_merge(amax, part[w]);
-    const float s = scale_of(amax);
-    if (threadIdx.x == 0) scale[row] = s;
-    int8_t* qr = q + row * ldq;
-    for (int64_t c = threadIdx.x; c < cols; c += 256) qr[c] = (int8_t)code_of(Elem<DT>::to_f32(h_at(c)), s);
-}
-
-// dev/test kernel: every 16-bit pattern g that glu_fast_ok admits through the shipped sequence (FASTDIV) and the specified one (`/`), against u = 1 and u = -1/2.
+// dev/test kernel: every 16-bit pattern g that fast_ok admits through the shipped sequence (FASTDIV) and the specified one (`/`), against u = 1 and u = -1/2.
 // out[0] += patterns admitted, out[1] += patterns whose stored h differs in either.
 template <int DT, int KIND>
 __global__ __launch_bounds__(256) void glu_short_check(float L, float alpha, uint32_t gmax_bits, unsigned long long* __restrict__ out) {
     const uint32_t pat = blockIdx.x * 256u + threadIdx.x;            // 256 blocks x 256 threads = all 65 536 patterns
     const uint32_t mag = pat & 0x7FFFu;
-    if (!glu_fast_ok<DT, KIND>(mag, mag, gmax_bits)) return;
+    const typename GluOp<KIND>::Params p{L, alpha, gmax_bits};
+    if (!GluOp<KIND>::template fast_ok<DT>(mag, mag, p)) return;
     const uint32_t one = DT == PQ_BF16 ? 0x3F80u : 0x3C00u, mhalf = DT == PQ_BF16 ? 0xBF00u : 0xB800u;
     const uint32_t gw = pat | (pat << 16), uw = one | (mhalf << 16);
     const v4u gv = v4u{gw, gw, gw, gw}, uv = v4u{uw, uw, uw, uw};
-    const v4u a = glu_vec<DT, KIND, true>(gv, uv, L, alpha), b = glu_vec<DT, KIND, false>(gv, uv, L, alpha);
+    const v4u a = GluOp<KIND>::template vec<DT, true>(gv, uv, p), b = GluOp<KIND>::template vec<DT, false>(gv, uv, p);
     atomicAdd(&out[0], 1ull);
     if (a[0] != b[0]) atomicAdd(&out[1], 1ull);
 }
@@ -280,71 +150,13 @@ void launch_glu_short_check(int dtype, int kind, float limit, float alpha, unsig
     }
 }
 
-template <int DT, int KIND, int TPR, bool WRITE_H>
-static void launch_glu_vec(int vpt, const uint8_t* g, int64_t ldg_b, const uint8_t* u, int64_t ldu_b, int64_t rows, int nvec, float L, float alpha, uint32_t gb,
-                           int8_t* q, int64_t ldq, float* scale, uint8_t* h, int64_t ldh_b, hipStream_t st) {
-    constexpr int BS = TPR > 256 ? TPR : 256, RPB = BS / TPR;
-    const dim3 grid((unsigned)((rows + RPB - 1) / RPB)), block(BS);
-#define PQ_GLU_LAUNCH(V) glu_quant_vec<DT, KIND, V, TPR, WRITE_H><<<grid, block, 0, st>>>(g, ldg_b, u, ldu_b, rows, nvec, L, alpha, gb, q, ldq, scale, h, ldh_b)
-    switch (vpt) {
-        case 1:
-            if constexpr (TPR != 512) PQ_GLU_LAUNCH(1);
-            break;
-        case 2:
-            if constexpr (TPR != 512) PQ_GLU_LAUNCH(2);
-            break;
-        case 3:
-            if constexpr (TPR == 512) PQ_GLU_LAUNCH(3);
-            break;
-        case 4:
-            if constexpr (TPR != 512) PQ_GLU_LAUNCH(4);
-            break;
-        case 8:
-            if constexpr (TPR == 256) PQ_GLU_LAUNCH(8);
-            break;
-        default:
-            if constexpr (TPR == 256) PQ_GLU_LAUNCH(16);
-            break;
-    }
-#undef PQ_GLU_LAUNCH
-}
-
-// Row layouts as silu_mul_quant_dispatch: one wave per row up to 256 vectors (4096 16-bit elements), 512 threads x 3 vectors for 1025 .. 1536 vectors, else 256
-// threads x 1 .. 16 vectors (up to 4096 vectors = 65 536 16-bit elements); anything else — ragged width, unaligned pointer or leading dimension — is generic.
-template <int DT, int KIND>
-static void glu_quant_dispatch_kind(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, float L, float alpha, uint32_t gb,
-                                    int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st) {
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    const bool vec_ok = (cols % EPV == 0) && (ldg % EPV == 0) && (ldu % EPV == 0) && aligned_to(g, 16) && aligned_to(u, 16) && (ldq % EPV == 0) &&
-                        aligned_to(q, EPV) && cols / EPV <= 256 * 16 && (!h_out || ((ldh % EPV == 0) && aligned_to(h_out, 16)));
-    if (!vec_ok) {
-        glu_quant_generic<DT, KIND><<<dim3((unsigned)rows), dim3(256), 0, st>>>(g, ldg, u, ldu, cols, L, alpha, q, ldq, scale, h_out, ldh);
-        return;
-    }
-    const int nvec = (int)(cols / EPV);
-    auto pow2 = [](int v) { int p = 1; while (p < v) p <<= 1; return p; };
-    const uint8_t* gb8 = reinterpret_cast<const uint8_t*>(g);
-    const uint8_t* ub8 = reinterpret_cast<const uint8_t*>(u);
-    uint8_t* hb = reinterpret_cast<uint8_t*>(h_out);
-    const int64_t kb = Elem<DT>::kBytes;
-#define PQ_GLU_ROWS(TPR, VPT)                                                                                                                          \
-    do {                                                                                                                                               \
-        if (h_out) launch_glu_vec<DT, KIND, TPR, true>(VPT, gb8, ldg * kb, ub8, ldu * kb, rows, nvec, L, alpha, gb, q, ldq, scale, hb, ldh * kb, st);   \
-        else launch_glu_vec<DT, KIND, TPR, false>(VPT, gb8, ldg * kb, ub8, ldu * kb, rows, nvec, L, alpha, gb, q, ldq, scale, hb, 0, st);               \
-    } while (0)
-    if (nvec <= 64 * 4) PQ_GLU_ROWS(64, pow2((nvec + 63) / 64));
-    else if (nvec > 1024 && nvec <= 1536) PQ_GLU_ROWS(512, 3);
-    else PQ_GLU_ROWS(256, pow2((nvec + 255) / 256));
-#undef PQ_GLU_ROWS
-}
-
 template <int DT>
 void glu_quant_dispatch(int kind, const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, float limit, float alpha, int8_t* q,
                         int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st) {
     const float L = glu_limit_in_dtype(DT, limit);
     const uint32_t gb = glu_gmax_bits(DT, alpha);
-    if (kind == GLU_CLAMPED_SILU) glu_quant_dispatch_kind<DT, GLU_CLAMPED_SILU>(g, ldg, u, ldu, rows, cols, L, alpha, gb, q, ldq, scale, h_out, ldh, st);
-    else glu_quant_dispatch_kind<DT, GLU_ALPHA_SIGMOID>(g, ldg, u, ldu, rows, cols, L, alpha, gb, q, ldq, scale, h_out, ldh, st);
+    if (kind == GLU_CLAMPED_SILU) rowmap_dispatch<GluOp<GLU_CLAMPED_SILU>, DT>(g, ldg, u, ldu, rows, cols, {L, alpha, gb}, q, ldq, scale, h_out, ldh, nullptr, st);
+    else rowmap_dispatch<GluOp<GLU_ALPHA_SIGMOID>, DT>(g, ldg, u, ldu, rows, cols, {L, alpha, gb}, q, ldq, scale, h_out, ldh, nullptr, st);
 }
 
 template void glu_quant_dispatch<PQ_BF16>(int, const void*, int64_t, const void*, int64_t, int64_t, int64_t, float, float, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);

@@ -1,6 +1,7 @@
-// producer_device.h — the device helpers shared by the producer-fused quantisation kernels (producer_kernels.hip: K1s, K1n; glu_kernels.hip: the clamped
-// gates of GPT-OSS and DeepSeek-V4): two-elements-per-instruction arithmetic, the QSPEC S1-S5 stage, and the second half of K1 (row amax + exact encode) on
-// a row of h held in registers.  Every function is __forceinline__: a translation unit that includes this header instantiates its own kernels only.
+// producer_device.h — the device helpers shared by the producer-fused quantisation kernels (rowmap_kernels.h: K1s, K1g, K1gg, K1u; rownorm_kernels.h: the norm
+// family): two-elements-per-instruction arithmetic, the arithmetic stages every activation is built from (the specified exponential, the division-free quotient,
+// the unpack / stage / pack wrapper, each stated ONCE), the QSPEC S1-S5 stage, and the second half of K1 (row amax + exact encode) on a row of h held in registers.
+// Every function is __forceinline__: a translation unit that includes this header instantiates its own kernels only.
 #pragma once
 #include <type_traits>
 
@@ -31,6 +32,99 @@ template <> struct Pair<PQ_FP16> {
     }
 };
 
+__device__ __forceinline__ float fbits(uint32_t u) { return __builtin_bit_cast(float, u); }
+
+// QSPEC S1-S4 on NP pairs: exp_spec(a) = p * 2^n (Cody-Waite + degree-7 Horner with fma), stage by stage (see silu_mul_stage).  The clamp is v_med3_f32 (a NaN comes
+// out finite: every caller puts the NaN back or divides a NaN by the result); CLAMP = false when the caller guarantees -30 <= a <= 100 (the clamp is then the
+// identity).  ldexp(p, n) equals the specification's two exact power-of-two multiplications for every n in [-43, 144].  PLUS1: out = 1 + exp_spec(a), the add
+// in the statement of the ldexp (where K1s and K1g had it: a loop of its own after this one gives them another schedule).
+template <int NP, bool CLAMP, bool PLUS1 = false>
+__device__ __forceinline__ void exp_spec_stage(const v2f (&a)[NP], v2f (&out)[NP]) {
+    v2f tc[NP], n[NP], r[NP], p[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        if constexpr (CLAMP) tc[k] = v2f{__builtin_amdgcn_fmed3f(a[k].x, -30.0f, 100.0f), __builtin_amdgcn_fmed3f(a[k].y, -30.0f, 100.0f)};
+        else tc[k] = a[k];
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) n[k] = tc[k] * splat(fbits(0x3FB8AA3Bu));
+#pragma unroll
+    for (int k = 0; k < NP; ++k) n[k] = v2f{__builtin_rintf(n[k].x), __builtin_rintf(n[k].y)};
+#pragma unroll
+    for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-fbits(0x3F317200u)), tc[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-fbits(0x35BFBE8Eu)), r[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) p[k] = pk_fma(splat(fbits(0x39500D01u)), r[k], splat(fbits(0x3AB60B61u)));
+    constexpr uint32_t kC[6] = {0x3C088889u, 0x3D2AAAABu, 0x3E2AAAABu, 0x3F000000u, 0x3F800000u, 0x3F800000u};
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) p[k] = pk_fma(p[k], r[k], splat(fbits(kC[c])));
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        if constexpr (PLUS1) out[k] = splat(1.0f) + v2f{__builtin_ldexpf(p[k].x, (int)n[k].x), __builtin_ldexpf(p[k].y, (int)n[k].y)};
+        else out[k] = v2f{__builtin_ldexpf(p[k].x, (int)n[k].x), __builtin_ldexpf(p[k].y, (int)n[k].y)};
+    }
+}
+
+// The IEEE quotient g / d without v_div_scale / v_div_fmas / v_div_fixup: the arithmetic core of the hardware's own correctly rounded sequence (rcp, one Newton
+// step, the quotient and two residual corrections) without the operand scaling.  Exact for 0 <= |g| <= 86 and d in [1, 2^125) (see silu_mul_stage).  A zero g loses
+// its sign in the residual steps: callers that care keep zeros out or need +0 from +0.  K1g's 1 / d hands it an array of ones (the product 1 * y folds to y).
+template <int NP>
+__device__ __forceinline__ void fast_div_stage(const v2f (&g)[NP], const v2f (&d)[NP], v2f (&out)[NP]) {
+    v2f y0[NP], y[NP], q[NP], e[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) y0[k] = v2f{__builtin_amdgcn_rcpf(d[k].x), __builtin_amdgcn_rcpf(d[k].y)};
+#pragma unroll
+    for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], y0[k], splat(1.0f));
+#pragma unroll
+    for (int k = 0; k < NP; ++k) y[k] = pk_fma(e[k], y0[k], y0[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) q[k] = g[k] * y[k];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], q[k], g[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) q[k] = pk_fma(e[k], y[k], q[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], q[k], g[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) out[k] = pk_fma(e[k], y[k], q[k]);
+}
+
+// one 16-byte vector of g and of u -> NP pairs of floats each -> stage(g, u, h) -> one 16-byte vector of h rounded to the storage dtype
+template <int DT, class Stage>
+__device__ __forceinline__ v4u map_vec(const v4u& gv, const v4u& uv, Stage&& stage) {
+    constexpr int NP = DT == PQ_F32 ? 2 : 4;
+    v2f g[NP], u[NP], h[NP];
+    v4u out;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        if constexpr (DT == PQ_F32) {
+            const uint32_t g0 = gv[2 * j], g1 = gv[2 * j + 1], u0 = uv[2 * j], u1 = uv[2 * j + 1];   // copies first (hipcc quirk)
+            g[j] = v2f{__builtin_bit_cast(float, g0), __builtin_bit_cast(float, g1)};
+            u[j] = v2f{__builtin_bit_cast(float, u0), __builtin_bit_cast(float, u1)};
+        } else {
+            const uint32_t gw = gv[j], uw = uv[j];
+            g[j] = Pair<DT>::unpack(gw);
+            u[j] = Pair<DT>::unpack(uw);
+        }
+    }
+    stage(g, u, h);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        if constexpr (DT == PQ_F32) {
+            const float hx = h[j].x, hy = h[j].y;   // copies first: bit_cast of a vector-element lvalue reads element 0
+            out[2 * j] = __builtin_bit_cast(uint32_t, hx);
+            out[2 * j + 1] = __builtin_bit_cast(uint32_t, hy);
+        } else {
+            out[j] = Pair<DT>::pack(h[j]);
+        }
+    }
+    return out;
+}
+
 // QSPEC S1-S5 on NP pairs at once, written stage by stage so that NP independent instructions follow each other: one
 // wave's dependent v_pk_fma chain leaves the VALU idle most of the time (measured: 2x off the issue rate), NP chains do
 // not.  Notes on the forms used:
@@ -52,7 +146,7 @@ template <> struct Pair<PQ_FP16> {
 //    correction (4 of ~40 VALU results per element) are dropped for bf16 / fp16 rows.
 template <int DT, bool FASTDIV, int NP, bool SHORT = false>
 __device__ __forceinline__ void silu_mul_stage(const v2f (&g)[NP], const v2f (&u)[NP], v2f (&h)[NP]) {
-    v2f tc[NP], n[NP], r[NP], p[NP], d[NP], sg[NP];
+    v2f d[NP], sg[NP];
     if constexpr (FASTDIV && SHORT && DT == PQ_BF16) {
         // bf16 rows on the fast-division domain: 1 + exp(-g) from the hardware's exp2 (v_exp_f32, ~1 ulp).  The STORED silu(g) is a function of
         // the 16-bit g alone, and on every one of the 34 136 patterns of the domain this sequence stores the value the specified polynomial
@@ -61,30 +155,14 @@ __device__ __forceinline__ void silu_mul_stage(const v2f (&g)[NP], const v2f (&u
         // 11-bit significand two patterns differ.)
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            const v2f a = g[k] * splat(-__builtin_bit_cast(float, 0x3FB8AA3Bu));          // -g * log2(e)
+            const v2f a = g[k] * splat(-fbits(0x3FB8AA3Bu));          // -g * log2(e)
             d[k] = splat(1.0f) + v2f{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
         }
     } else {
+        v2f a[NP];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) tc[k] = v2f{__builtin_amdgcn_fmed3f(-g[k].x, -30.0f, 100.0f), __builtin_amdgcn_fmed3f(-g[k].y, -30.0f, 100.0f)};
-#pragma unroll
-    for (int k = 0; k < NP; ++k) n[k] = tc[k] * splat(__builtin_bit_cast(float, 0x3FB8AA3Bu));
-#pragma unroll
-    for (int k = 0; k < NP; ++k) n[k] = v2f{__builtin_rintf(n[k].x), __builtin_rintf(n[k].y)};
-#pragma unroll
-    for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-__builtin_bit_cast(float, 0x3F317200u)), tc[k]);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) r[k] = pk_fma(n[k], splat(-__builtin_bit_cast(float, 0x35BFBE8Eu)), r[k]);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) p[k] = pk_fma(splat(__builtin_bit_cast(float, 0x39500D01u)), r[k], splat(__builtin_bit_cast(float, 0x3AB60B61u)));
-    constexpr uint32_t kC[6] = {0x3C088889u, 0x3D2AAAABu, 0x3E2AAAABu, 0x3F000000u, 0x3F800000u, 0x3F800000u};
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k) p[k] = pk_fma(p[k], r[k], splat(__builtin_bit_cast(float, kC[c])));
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) d[k] = splat(1.0f) + v2f{__builtin_ldexpf(p[k].x, (int)n[k].x), __builtin_ldexpf(p[k].y, (int)n[k].y)};
+        for (int k = 0; k < NP; ++k) a[k] = v2f{-g[k].x, -g[k].y};
+        exp_spec_stage<NP, true, true>(a, d);
     }
     if constexpr (FASTDIV && SHORT) {
         v2f y0[NP], q[NP], e[NP];
@@ -97,23 +175,7 @@ __device__ __forceinline__ void silu_mul_stage(const v2f (&g)[NP], const v2f (&u
 #pragma unroll
         for (int k = 0; k < NP; ++k) sg[k] = pk_fma(e[k], y0[k], q[k]);
     } else if constexpr (FASTDIV) {
-        v2f y0[NP], y[NP], q[NP], e[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) y0[k] = v2f{__builtin_amdgcn_rcpf(d[k].x), __builtin_amdgcn_rcpf(d[k].y)};
-#pragma unroll
-        for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], y0[k], splat(1.0f));
-#pragma unroll
-        for (int k = 0; k < NP; ++k) y[k] = pk_fma(e[k], y0[k], y0[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) q[k] = g[k] * y[k];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], q[k], g[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) q[k] = pk_fma(e[k], y[k], q[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) e[k] = pk_fma(-d[k], q[k], g[k]);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) sg[k] = pk_fma(e[k], y[k], q[k]);
+        fast_div_stage<NP>(g, d, sg);
     } else {
 #pragma unroll
         for (int k = 0; k < NP; ++k) sg[k] = v2f{g[k].x / d[k].x, g[k].y / d[k].y};
@@ -125,11 +187,12 @@ __device__ __forceinline__ void silu_mul_stage(const v2f (&g)[NP], const v2f (&u
 #pragma unroll
     for (int k = 0; k < NP; ++k) h[k] = sg[k] * u[k];
 }
-template <int DT>
-__device__ __forceinline__ float silu_mul_spec(float g, float u) {
+// one element through a stage (the specified sequence of the generic kernels): the first lane of one pair
+template <class Stage>
+__device__ __forceinline__ float map_one(float g, float u, Stage&& stage) {
     const v2f ga[1] = {v2f{g, g}}, ua[1] = {v2f{u, u}};
     v2f h[1];
-    silu_mul_stage<DT, false, 1>(ga, ua, h);
+    stage(ga, ua, h);
     return h[0].x;
 }
 
@@ -157,33 +220,7 @@ template <int DT> __device__ __forceinline__ bool silu_fast_div_ok(uint32_t mn, 
 // one 16-byte vector of g and of u -> one 16-byte vector of h in the storage dtype
 template <int DT, bool FASTDIV, bool SHORT = (DT != PQ_F32)>
 __device__ __forceinline__ v4u silu_mul_vec(const v4u& gv, const v4u& uv) {
-    constexpr int NP = DT == PQ_F32 ? 2 : 4;
-    v2f g[NP], u[NP], h[NP];
-    v4u out;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        if constexpr (DT == PQ_F32) {
-            const uint32_t g0 = gv[2 * j], g1 = gv[2 * j + 1], u0 = uv[2 * j], u1 = uv[2 * j + 1];   // copies first (hipcc quirk)
-            g[j] = v2f{__builtin_bit_cast(float, g0), __builtin_bit_cast(float, g1)};
-            u[j] = v2f{__builtin_bit_cast(float, u0), __builtin_bit_cast(float, u1)};
-        } else {
-            const uint32_t gw = gv[j], uw = uv[j];
-            g[j] = Pair<DT>::unpack(gw);
-            u[j] = Pair<DT>::unpack(uw);
-        }
-    }
-    silu_mul_stage<DT, FASTDIV, NP, SHORT && DT != PQ_F32>(g, u, h);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        if constexpr (DT == PQ_F32) {
-            const float hx = h[j].x, hy = h[j].y;   // copies first: bit_cast of a vector-element lvalue reads element 0
-            out[2 * j] = __builtin_bit_cast(uint32_t, hx);
-            out[2 * j + 1] = __builtin_bit_cast(uint32_t, hy);
-        } else {
-            out[j] = Pair<DT>::pack(h[j]);
-        }
-    }
-    return out;
+    return map_vec<DT>(gv, uv, [](const auto& g, const auto& u, auto& h) { silu_mul_stage<DT, FASTDIV, DT == PQ_F32 ? 2 : 4, SHORT && DT != PQ_F32>(g, u, h); });
 }
 
 // division-free exact encode (quant_device.h) of one 16-byte vector of h, two elements per instruction

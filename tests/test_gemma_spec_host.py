@@ -267,15 +267,36 @@ def test_geglu_object_holds_every_layout_without_scratch():
     for dt in range(3):
         for wh in "01":
             for v, tpr in ((1, 64), (2, 64), (4, 64), (3, 512), (1, 256), (2, 256), (4, 256), (8, 256), (16, 256)):
-                assert len([n for n in k if re.search(r"\d+gelu_mul_quant_vecILi%dELi%dELi%dELb%sEE" % (dt, v, tpr, wh), n)]) == 1, (dt, v, tpr, wh)
-        assert len([n for n in k if re.search(r"\d+gelu_mul_quant_genericILi%dEE" % dt, n)]) == 1, dt
+                assert len([n for n in k if re.search(r"\d+rowmap_quant_rowsINS_7GegluOpELi%dELi%dELi%dELb%sELi0EEE" % (dt, v, tpr, wh), n)]) == 1, (dt, v, tpr, wh)
+        assert len([n for n in k if re.search(r"\d+rowmap_quant_genericINS_7GegluOpELi%dELi0EEE" % dt, n)]) == 1, dt
     assert len(k) == 3 * (2 * 9 + 1)
+    _no_scratch_no_spills(k)
+
+
+def test_k1s_object_holds_exactly_the_layouts_of_the_dispatchers_ladder():
+    """K1s and its split halves (producer_kernels.o): per dtype, MODE 0 with and without h_out, MODE 1 and MODE 2 of silu * u, and the two identity modes, each at the
+    (threads per row, vectors per thread) pairs of rowmap_dispatch's ladder and no others; the identity never takes 512 threads per row.  The ladder's (256, 1) is
+    instantiated but no width reaches it (rows of up to 256 vectors take a wave): it is held here as it is in the counts of K1g, K1gg and K1u."""
+    k = {n: v for n, v in _kernels_of("producer_kernels").items() if "rowmap_quant_" in n}
+    ladder = ((64, 1), (64, 2), (64, 4), (512, 3), (256, 1), (256, 2), (256, 4), (256, 8), (256, 16))
+    forms = (("9SiluMulOp", 0, "01"), ("9SiluMulOp", 1, "0"), ("9SiluMulOp", 2, "0"), ("7IdentOp", 1, "0"), ("7IdentOp", 2, "0"))
+    want = set()
+    for dt in range(3):
+        for op, mode, whs in forms:
+            for wh in whs:
+                for tpr, v in ladder:
+                    if not (op == "7IdentOp" and tpr == 512):
+                        want.add("rowsINS_%sELi%dELi%dELi%dELb%sELi%dEEE" % (op, dt, v, tpr, wh, mode))
+            want.add("genericINS_%sELi%dELi%dEEE" % (op, dt, mode))
+    got = {re.search(r"rowmap_quant_(\w+?EEE)v", n).group(1) for n in k}
+    assert got == want, (sorted(got - want), sorted(want - got))
+    assert len(k) == len(want) == 3 * (4 * 9 + 2 * 8 + 5)
     _no_scratch_no_spills(k)
 
 
 @pytest.mark.parametrize("obj,count", [("producer_kernels", None), ("addnorm_kernels", 57), ("act_kernels", None), ("glu_kernels", None)])
 def test_the_existing_objects_hold_no_kernel_of_the_new_family(obj, count):
     k = _kernels_of(obj)
-    assert k and not [n for n in k if re.search(r"gemma_rmsnorm_quant|gelu_mul_quant", n)], obj
+    assert k and not [n for n in k if re.search(r"gemma_rmsnorm_quant|gelu_mul_quant|GegluOp", n)], obj
     if count is not None:
         assert len(k) == count

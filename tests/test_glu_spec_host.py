@@ -181,8 +181,8 @@ def test_glu_code_object_has_no_scratch_and_the_expected_kernels():
         elif m and name:
             kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
     # 3 dtypes x 2 kinds x with / without h_out x (one wave per row: 1, 2, 4 vectors | 256 threads: 1, 2, 4, 8, 16 | 512 threads: 3)
-    assert len([k for k in kernels if "glu_quant_vec" in k]) == 3 * 2 * 2 * 9
-    assert len([k for k in kernels if "glu_quant_generic" in k]) == 3 * 2
+    assert len([k for k in kernels if "rowmap_quant_rowsINS_5GluOp" in k]) == 3 * 2 * 2 * 9
+    assert len([k for k in kernels if "rowmap_quant_genericINS_5GluOp" in k]) == 3 * 2
     assert len([k for k in kernels if "glu_short_check" in k]) == 2 * 2
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)

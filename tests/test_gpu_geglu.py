@@ -21,6 +21,8 @@ U_VALUES = (1.0, -1.0, 0.5, -2.0, 3.140625, 0.333251953125, 1e-3, 300.0, -0.0751
 # one vector (f32: two); one wave x 2 vectors (f32: x 4); ragged in vectors (87 / 174); 256 threads x 2 (f32: x 4); 512 threads x 3 (16-bit 9216 = f32 4608 = 1152 vectors);
 # 256 threads x 8 (f32: x 16, the vector limit); a ragged width (generic)
 WIDTHS = (8, 640, 696, 2816, 9216, 16384, 333)
+# then every boundary of the family's layout ladder (rowmap_dispatch) in 16-byte vectors, as widths of 16-bit rows (8 elements per vector) and of f32 rows (4)
+WIDTHS += tuple(c for c in sorted({v * e for v in [1, 64, 65, 128, 256, 257, 512, 1024, 1025, 1536, 1537, 2048, 4096] for e in (8, 4)}) if c not in WIDTHS)
 
 
 @pytest.fixture(scope="module")

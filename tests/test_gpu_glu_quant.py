@@ -51,8 +51,8 @@ def _call_guarded(g_t, u_t, code, kname, limit, alpha, want_h=True, margin=64):
 
 
 # widths in elements: one wave per row (<= 256 vectors), 256 threads x 1 .. 16 vectors, 512 threads x 3 vectors (1025 .. 1536 vectors), the real widths 2880 (GPT-OSS) and
-# 2048 k, the widest rows a block holds (4096 vectors)
-WIDTHS_16 = [8, 64, 512, 1000, 2048, 2880, 4096, 6144, 11008, 14336, 32768]
+# 2048 k, the widest rows a block holds (4096 vectors); then every boundary of the family's ladder (rowmap_dispatch) in vectors: 65, 128, 257, 1024, 1025, 1536, 1537, 2048
+WIDTHS_16 = [8, 64, 512, 1000, 2048, 2880, 4096, 6144, 11008, 14336, 32768, 520, 1024, 2056, 8192, 8200, 12288, 12296, 16384]
 
 
 @pytest.mark.parametrize("kname,kind,limit,alpha", KINDS, ids=[k[0] for k in KINDS])
@@ -74,9 +74,29 @@ def test_every_row_layout_against_the_spec(pq, kname, kind, limit, alpha, code):
 
 @pytest.mark.parametrize("kname,kind,limit,alpha", KINDS, ids=[k[0] for k in KINDS])
 @pytest.mark.parametrize("code", [0, 1, 2], ids=["bf16", "fp16", "f32"])
+def test_wide_rows_with_256_threads(pq, pq_opt, kname, kind, limit, alpha, code):
+    """rows of 1025 .. 1536 vectors take 512 threads x 3 vectors; PQ_SILU_TPR=256 sends them to 256 threads x 8, as for K1s, K1u and K1gg.  Time only, never bits."""
+    cols = 1300 * (4 if code == 2 else 8)
+    gu = _rows(np.random.default_rng(400 + 10 * kind + code), 3, 2 * cols, code)
+    gu_t = to_gpu(gu, code)
+    g_t, u_t = gu_t[:, :cols], gu_t[:, cols:]
+    want_q, want_s, want_h = G.glu_quantize(gu[:, :cols], gu[:, cols:], code, kind, limit, alpha or 0.0)
+    d, hd = pq.glu_quantize(g_t, u_t, kname, limit, alpha, return_h=True)
+    pq_opt("PQ_SILU_TPR", 256)
+    qt, h = pq.glu_quantize(g_t, u_t, kname, limit, alpha, return_h=True)
+    q2 = pq.glu_quantize(g_t, u_t, kname, limit, alpha)
+    for t, tag in ((qt, ""), (q2, " (no h)")):
+        same(t.int_data, want_q, f"{kname} PQ_SILU_TPR=256: q{tag}"); same(t.scale, want_s, f"{kname} PQ_SILU_TPR=256: scale{tag}")
+        assert torch.equal(t.int_data, d.int_data) and torch.equal(t.scale.view(torch.int32), d.scale.view(torch.int32)), "the switch changed a bit"
+    same_f(h, want_h, code, f"{kname} PQ_SILU_TPR=256: h")
+    assert torch.equal(h.view(torch.uint8), hd.view(torch.uint8)), "the switch changed a bit of h"
+
+
+@pytest.mark.parametrize("kname,kind,limit,alpha", KINDS, ids=[k[0] for k in KINDS])
+@pytest.mark.parametrize("code", [0, 1, 2], ids=["bf16", "fp16", "f32"])
 def test_generic_kernel_odd_widths_and_unaligned_leading_dimensions(pq, kname, kind, limit, alpha, code):
     rng = np.random.default_rng(200 + 10 * kind + code)
-    for cols, pad in ((1, 0), (7, 3), (129, 1), (1001, 5), (2881, 2), (640, 1)):
+    for cols, pad in ((1, 0), (7, 3), (129, 1), (1001, 5), (2881, 2), (640, 1), (50257, 2)):
         rows = 5
         ga, ua = _rows(rng, rows, cols + pad + 1, code), _rows(rng, rows, cols + pad + 1, code)
         g_t, u_t = to_gpu(ga, code)[:, 1:cols + 1], to_gpu(ua, code)[:, 1:cols + 1]                    # odd leading dimension, base off the 16-byte grid

@@ -33,8 +33,12 @@ def _split(n, parts):
     return out
 
 
+# one block per row at every boundary of the family's layout ladder (rowmap_dispatch) in 16-byte vectors, as widths of 16-bit rows (8 elements per vector) and of f32 rows (4)
+LADDER = [(3, c, 1) for c in sorted({v * e for v in [1, 64, 65, 128, 256, 257, 512, 1024, 1025, 1536, 1537, 2048, 4096] for e in (8, 4)})]
+
+
 @pytest.mark.parametrize("code", [0, 1, 2])
-@pytest.mark.parametrize("rows,cols,parts", [(64, 4096, 8), (37, 3584, 1), (5, 1000, 3), (130, 11008, 8), (3, 77, 2), (9, 28672, 8), (16, 40000, 2)])
+@pytest.mark.parametrize("rows,cols,parts", [(64, 4096, 8), (37, 3584, 1), (5, 1000, 3), (130, 11008, 8), (3, 77, 2), (9, 28672, 8), (16, 40000, 2)] + LADDER)
 def test_split_silu_quant_equals_the_fused_kernel_and_the_oracle(pq, code, rows, cols, parts):
     """column blocks: local amax per block (vector and generic layouts, ragged and unaligned widths), integer max over the blocks, encode per block == the oracle's
     S1-S6 on the whole row and == the one-pass kernel; special values (NaN, Inf, zero rows) propagate exactly as in K1s."""
@@ -66,7 +70,7 @@ def test_split_silu_quant_equals_the_fused_kernel_and_the_oracle(pq, code, rows,
 
 
 @pytest.mark.parametrize("code", [0, 1, 2])
-@pytest.mark.parametrize("rows,cols,parts", [(64, 8192, 8), (37, 1024, 1), (5, 1000, 3), (130, 4096, 4), (3, 77, 2), (16, 40000, 2)])
+@pytest.mark.parametrize("rows,cols,parts", [(64, 8192, 8), (37, 1024, 1), (5, 1000, 3), (130, 4096, 4), (3, 77, 2), (16, 40000, 2)] + [c for c in LADDER if c[1] != 1024])
 def test_split_plain_quant_equals_k1_and_the_oracle(pq, code, rows, cols, parts):
     """the same two halves for a PLAIN activation (pq_quant_rowamax / pq_quant_rowwise_amax: a rank's heads of the attention output): block amax, integer max over the
     blocks, encode per block == the oracle's Q1-Q6 on the whole row == K1; NaN / Inf / zero rows included."""

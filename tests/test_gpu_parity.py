@@ -840,9 +840,14 @@ def test_golden_silu_mul_quantize(pq, producer_golden):
     same(qt2.int_data, g["q"], "silu q (no h)"); same(qt2.scale, g["scale"], "silu scale (no h)")
 
 
+# every boundary of the family's layout ladder (rowmap_dispatch) in 16-byte vectors, as widths of 16-bit rows (8 elements per vector) and of f32 rows (4)
+LADDER_VECTORS = [1, 64, 65, 128, 256, 257, 512, 1024, 1025, 1536, 1537, 2048, 4096]
+LADDER_COLS = sorted({v * e for v in LADDER_VECTORS for e in (8, 4)})
+
+
 @pytest.mark.parametrize("code", [0, 1, 2])
 @pytest.mark.parametrize("rows,cols", [(1, 1), (7, 13), (33, 1000), (64, 4096), (5, 11008), (3, 28672), (2, 40000), (300, 512),
-                                       (1, 8), (130, 2048), (2, 65536 + 8)])
+                                       (1, 8), (130, 2048), (2, 65536 + 8)] + [(3, c) for c in LADDER_COLS if c not in (8, 512, 2048, 4096)])
 def test_silu_mul_quant_vs_oracle(pq, code, rows, cols):
     """Vector path (16-byte aligned widths up to 4096 vectors) and generic path (ragged / very wide), g and u as the two
     column halves of ONE [rows, 2*cols] matrix (how a fused gate+up GEMM hands them over) and as separate tensors."""

@@ -5,7 +5,7 @@ it, and the fragment of the kernel name the row expects to launch.  A shape that
 shapes before it launches.  Every result is compared bit for bit with the oracle and with the bits of the default setting in the same process.
 
 That the rows REACH their kernels is not something bits can show: the three files test_gpu_k_rotation.py, test_gpu_switch_paths.py and test_gpu_grouped_edges.py were run
-once under a kernel trace on an MI355X, the list of kernel names and call counts is profiles/r08_switch_paths_kernels.txt, and tests/test_switch_coverage.py (CPU)
+once under a kernel trace on an MI355X, the list of kernel names and call counts is profiles/r21_switch_paths_kernels.txt, and tests/test_switch_coverage.py (CPU)
 holds every fragment below against that list.
 
 PQ_SP128_LC=2 (12 waves) exists only in ablation builds (PQ_ABLATION_BUILD, gemm_s8_fast.hip): the shipped library treats it as 1, so it has no row."""
@@ -17,7 +17,7 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import qspec_numpy as Q
-from tests.gpu_util import TD, bits, same, to_gpu
+from tests.gpu_util import TD, bits, same, same_f, to_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -49,11 +49,16 @@ TABLE = [
     *[Row(sw, v, "k2", "rpb = plan(k2_blocks > 0 ? k2_blocks : default, strips, batch): rows per workgroup of the amax / the encode pass, vectorised and scalar form",
           K2_SHAPES, ["col_amax<0, true>", "col_amax<0, false>", "col_encode<1, true>", "col_encode<2, false>"])
       for sw in ("PQ_K2_BLOCKS_A", "PQ_K2_BLOCKS_E") for v in ("1", "7", "100000")],
-    # ---- K1s (producer_kernels.hip, silu_mul_quant_dispatch / silu_mul_split_dispatch)
+    # ---- K1s (producer_kernels.hip, silu_mul_quant_dispatch / silu_mul_split_dispatch; the ladder is rowmap_dispatch's, rowmap_kernels.h)
     Row("PQ_SILU_TPR", "256", "silu", "nvec > 1024 && nvec <= 1536 && opt().silu_tpr != 256 -> 512 threads x 3 vectors; with the switch: 256 threads x 8",
         [(33, 8200, 0), (130, 11008, 0), (9, 12288, 1), (33, 4100, 2), (17, 6144, 2)],
-        ["silu_mul_quant_vec<0, 8, 256, false, 0, false>", "silu_mul_quant_vec<0, 8, 256, true, 0, false>", "silu_mul_quant_vec<1, 8, 256, false, 1, false>",
-         "silu_mul_quant_vec<2, 8, 256, false, 2, false>", "silu_mul_quant_vec<0, 3, 512, false, 0, false>"]),
+        ["rowmap_quant_rows<pq::SiluMulOp, 0, 8, 256, false, 0>", "rowmap_quant_rows<pq::SiluMulOp, 0, 8, 256, true, 0>", "rowmap_quant_rows<pq::SiluMulOp, 1, 8, 256, false, 1>",
+         "rowmap_quant_rows<pq::SiluMulOp, 2, 8, 256, false, 2>", "rowmap_quant_rows<pq::SiluMulOp, 0, 3, 512, false, 0>"]),
+    # ---- K1g (glu_kernels.hip, glu_quant_dispatch): the same ladder (rowmap_dispatch), both kinds
+    Row("PQ_SILU_TPR", "256", "glu", "nvec > 1024 && nvec <= 1536 && opt().silu_tpr != 256 -> 512 threads x 3 vectors; with the switch: 256 threads x 8",
+        [(33, 8200, 0), (9, 12288, 1), (17, 6144, 2)],
+        ["rowmap_quant_rows<pq::GluOp<0>, 0, 8, 256, false, 0>", "rowmap_quant_rows<pq::GluOp<1>, 0, 8, 256, true, 0>", "rowmap_quant_rows<pq::GluOp<0>, 1, 8, 256, true, 0>",
+         "rowmap_quant_rows<pq::GluOp<1>, 2, 8, 256, false, 0>", "rowmap_quant_rows<pq::GluOp<0>, 0, 3, 512, false, 0>"]),
     # ---- the weight-streaming kernel (gemm_s8_skinny.hip, skinny_plan / launch_gemm_skinny)
     *[Row("PQ_SKINNY_RB", v, "skinny", "if (const int f = opt().skinny_rb; f && mt <= 2) rb = f   [mt = ceil(M / 16)]",
           [(M, N, 1024) for M in (1, 16, 17, 32) for N in SKINNY_N], [f"gemm_s8_skinny<0, 1, {v}, true>", f"gemm_s8_skinny<3, 2, {v}, true>", f"gemm_s8_skinny<2, 1, {v}, false>"])
@@ -197,6 +202,32 @@ def _run_silu(pq, pq_opt, row):
         assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1].view(torch.uint8), res[1][1].view(torch.uint8))
 
 
+def _run_glu(pq, pq_opt, row):
+    from tests import glu_spec as G
+    for rows, cols, code in row.shapes:
+        nvec = cols // _epv(code)
+        assert cols % _epv(code) == 0 and 1024 < nvec <= 1536
+        rng = np.random.default_rng(rows * 137 + cols + code)
+        g = (rng.standard_normal((rows, cols)) * 4).astype(np.float32)
+        u = (rng.standard_normal((rows, cols)) * 4).astype(np.float32)
+        if code != 2:
+            g, u = Q.from_f32(g, code), Q.from_f32(u, code)
+        gt, ut = to_gpu(g, code), to_gpu(u, code)
+        for kname, kind, alpha in (("clamped_silu", G.CLAMPED_SILU, None), ("alpha_sigmoid", G.ALPHA_SIGMOID, 1.702)):
+            want_q, want_s, want_h = G.glu_quantize(g, u, code, kind, 7.0, alpha or 0.0)
+            res = []
+            for value in ("", row.value):
+                pq_opt(row.switch, value)
+                qt, h = pq.glu_quantize(gt, ut, kname, 7.0, alpha, return_h=True)
+                q2 = pq.glu_quantize(gt, ut, kname, 7.0, alpha)
+                what = f"{row.switch}={value!r} {kname} {rows}x{cols}/{code}"
+                same(qt.int_data, want_q, what + " q"); same(qt.scale, want_s, what + " scale"); same_f(h, want_h, code, what + " h")
+                same(q2.int_data, want_q, what + " q (no h)"); same(q2.scale, want_s, what + " scale (no h)")
+                res.append((qt.int_data, h))
+            pq_opt(row.switch, "")
+            assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1].view(torch.uint8), res[1][1].view(torch.uint8))
+
+
 def _gemm_operands(M, N, K, seed):
     rng = np.random.default_rng(seed)
     a = rng.integers(-128, 128, (M, K), dtype=np.int8); b = rng.integers(-128, 128, (N, K), dtype=np.int8)
@@ -263,7 +294,7 @@ def _run_plan(pq, pq_opt, row):
     assert np.array_equal(bits(y1[torch.tensor(rows, device="cuda")]), Q.epilogue(acc[rows], xs[rows], ws, bias[0], 0))
 
 
-RUNNERS = {"k1": _run_k1, "k1_fallback": _run_k1_fallback, "k2": _run_k2, "silu": _run_silu, "skinny": _run_skinny, "gemm:ring128": _run_gemm, "gemm:sp128_16": _run_gemm,
+RUNNERS = {"k1": _run_k1, "k1_fallback": _run_k1_fallback, "k2": _run_k2, "silu": _run_silu, "glu": _run_glu, "skinny": _run_skinny, "gemm:ring128": _run_gemm, "gemm:sp128_16": _run_gemm,
            "plan": _run_plan}
 
 

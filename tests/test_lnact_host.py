@@ -161,8 +161,8 @@ def test_code_objects_have_every_layout_and_no_scratch():
     for dt in range(3):
         for kind in range(3):
             # wave per row x 1 / 2 / 4, 512 threads x 3, 256 threads x 1 .. 16, each with / without h_out; one generic kernel
-            assert len([k for k in ka if re.search(r"act_quant_vecILi%dELi%dE" % (dt, kind), k)]) == (3 + 1 + 5) * 2, (dt, kind)
-            assert len([k for k in ka if re.search(r"act_quant_genericILi%dELi%dE" % (dt, kind), k)]) == 1, (dt, kind)
+            assert len([k for k in ka if re.search(r"rowmap_quant_rowsINS_5ActOpILi%dEEELi%dE" % (kind, dt), k)]) == (3 + 1 + 5) * 2, (dt, kind)
+            assert len([k for k in ka if re.search(r"rowmap_quant_genericINS_5ActOpILi%dEEELi%dE" % (kind, dt), k)]) == 1, (dt, kind)
     assert len(ka) == 9 * 19
     for k, v in list(kl.items()) + list(ka.items()):
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)

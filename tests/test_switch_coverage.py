@@ -2,7 +2,7 @@
 
 The header and pq_common.h promise of most switches "time only, never bits"; the A/B tools under tools/ measure with them and the planners' defaults were chosen from
 those measurements.  A switch nobody launches under the suite is compiled device code (or launch geometry) that has never executed there, so a new switch needs a GPU test
-that names it.  The second test ties the table of tests/test_gpu_switch_paths.py to the kernel trace recorded on an MI355X (profiles/r08_switch_paths_kernels.txt):
+that names it.  The second test ties the table of tests/test_gpu_switch_paths.py to the kernel trace recorded on an MI355X (profiles/r21_switch_paths_kernels.txt):
 every kernel a row says it reaches was really launched by the three switch / rotation / grouped files."""
 import glob
 import os
@@ -53,7 +53,7 @@ def test_the_library_knows_exactly_the_table_names():
 
 
 def _traced_kernels():
-    path = os.path.join(ROOT, "profiles", "r08_switch_paths_kernels.txt")
+    path = os.path.join(ROOT, "profiles", "r21_switch_paths_kernels.txt")
     return [l.split(None, 1)[1].strip() for l in open(path) if l.strip() and not l.startswith("#")]
 
 
