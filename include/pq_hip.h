@@ -248,6 +248,15 @@ int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, in
 int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t axis,
                    int64_t rows, int64_t cols, void* out, int64_t ld_out, int32_t out_dtype, void* stream);
 
+/* OPERANDS OF THE DENSE GEMM ENTRIES (pq_gemm_s8s8s32, pq_qlinear_s8, pq_qlinear_s8_t, pq_qlinear_s8_kslabs, pq_qlinear_dyn): a[M, K] and b[N, K] are row-major int8
+ * with leading dimensions lda, ldb >= K in elements (for stacked codes lda >= k_per_slab), the output has ldy >= N (ldyt >= M); a smaller one is PQ_ERR_BAD_ARG before
+ * any HIP call.  Any such operands give the same bits; which kernel runs depends on them.  The MFMA tiles and the weight-streaming kernel need 16-byte aligned bases of
+ * a and b, lda and ldb multiples of 16 and below 2^23 (their loaders keep 255 rows x ld in a 32-bit offset), and K a positive multiple of 128: a column window of a
+ * wider buffer qualifies when it starts on a 16-byte boundary (no 128- or 256-byte alignment is needed).  Everything else — an odd base or leading dimension, ld >= 2^23,
+ * any other K — runs the generic kernel: about 300 TOPS where the tiles do 2000+, and about 50 when the rows are not 16-byte aligned.  pq_gemm_variant_name(M, N, K,
+ * lda, ldb) answers for the leading dimensions it is given and ASSUMES 16-byte aligned bases: "generic64" for operands that leave the fast path by their leading
+ * dimensions or K (also when PQ_FORCE_VARIANT names a tile); it cannot see a misaligned base.  The workspace queries take no leading dimensions and assume the fast path. */
+
 /* K3 debug/parity twin — c[M,N] = sum_k a[M,k] * b[N,k], exact int32: the drop-in for
  * torch._int_mm(a, b.t()) (aten::_int_mm), which BASELINE.json names as the CPU oracle. */
 int32_t pq_gemm_s8s8s32(const int8_t* a, int64_t lda, const int8_t* b, int64_t ldb,

@@ -986,6 +986,9 @@ int32_t pq_qlinear_dyn(const void* x, int32_t dtype, int64_t ld_x, const int8_t*
     CallScope scope_;           // K1 and the GEMM of this call plan and launch under ONE snapshot
     if (const int32_t rc = check_dtype("pq_qlinear_dyn", dtype)) return rc;
     if (M < 0 || N < 0 || K < 0) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_dyn: negative size");
+    // (before the workspace check and before K1 launches: K1 would name itself for ld_x, and would already have run when pq_qlinear_s8 refused ldw or ldy)
+    if (bad_mat(x, M, K, ld_x) || bad_mat(w, N, K, ldw) || bad_mat(y, M, N, ldy) || (N > 0 && !w_scale))
+        return fail(PQ_ERR_BAD_ARG, "pq_qlinear_dyn: bad arguments (M=%lld N=%lld K=%lld ld_x=%lld ldw=%lld ldy=%lld)", (long long)M, (long long)N, (long long)K, (long long)ld_x, (long long)ldw, (long long)ldy);
     if (M == 0 || N == 0) return PQ_OK;
     if (const int32_t rc = check_workspace("pq_qlinear_dyn", workspace, workspace_bytes, pq_qlinear_dyn_workspace_bytes(M, N, K), 256)) return rc;
     uint8_t* base = static_cast<uint8_t*>(workspace);
