@@ -233,7 +233,25 @@ int32_t pq_gemma_postnorm_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x,
                                                     int64_t ld_s, const void* weight, float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale,
                                                     void* h_out, int64_t ld_h, void* stream);
 
-/* K1gg — K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
+/* K1oq — the post-norm residual flow of OLMo-2 / OLMo-3 in one launch: the norm of the sublayer output, the residual add and K1 on the sum.  Per row, with x the sublayer
+ * output and residual the residual stream (QSPEC NO1-NO5, PO1, A1, Q1-Q6):
+ *   p = cast_rne((f32(x) * rs) * f32(post_weight))      NO1-NO5: N1-N4's sum of squares and rs, binary32 throughout, ONE storage rounding, gain w; never written (PO1)
+ *   sum_out = cast_rne(f32(residual) + f32(p))          STORED: the new residual stream (A1)
+ *   then Q1-Q6 on the rows of sum_out AS STORED -> q, scale (there is no second norm and no h_out: what is quantised is sum_out itself).
+ * The three forms, by which operands are null:
+ *   K1oq  every operand given.
+ *   K1oa  q == scale == NULL: stores sum_out alone (the end of a chain).
+ *   K1on  residual == NULL and q == scale == NULL: stores p itself to sum_out (the norm alone: q_norm / k_norm; ld_r is not read).
+ * q and scale go together, and q needs residual: a partly-null group is PQ_ERR_BAD_ARG naming the missing argument.  post_weight: [cols] of `dtype`.  Row layouts and the
+ * PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time only, never bits).
+ * Aliasing: sum_out may BE x or residual (same pointer and leading dimension; the whole row of x is read before any of sum_out is written) — with residual == NULL, x
+ * alone; any other overlap of sum_out with an input, and any overlap of q or scale with an input, sum_out or each other, is refused.  A null x / post_weight / sum_out,
+ * ld < cols, cols >= 2^24, a negative or non-finite post_eps and an unknown dtype are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.
+ * rows == 0 or cols == 0: nothing is read or written, returns PQ_OK (the scales of empty rows are 1, QSPEC Q3: the caller's). */
+int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const void* post_weight, float post_eps, const void* residual, int64_t ld_r, void* sum_out,
+                                           int64_t ld_s, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* stream);
+
+/* K1gg— K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6
  * on the rows of h — the eager chain op for op (the activation is stored, then multiplied).  kind: PQ_ACT_GELU_TANH only; anything else is PQ_ERR_BAD_ARG naming `kind`.

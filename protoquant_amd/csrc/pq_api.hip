@@ -519,6 +519,32 @@ int32_t pq_gemma_postnorm_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x,
     return check_launch(fn);
 }
 
+int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const void* post_weight, float post_eps, const void* residual, int64_t ld_r, void* sum_out,
+                                           int64_t ld_s, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* stream) {
+    Range range_("pq:olmo_postnorm_add_quant (K1oq / K1oa / K1on)");
+    const char* fn = "pq_olmo_postnorm_add_quant_rowwise";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const bool quant = q || scale;                 // K1oq: the group is checked as a whole; otherwise K1oa (residual given) or K1on (the norm alone)
+    const bool add = quant || residual;
+    const char* group = " (q and scale go together: both null is the form that stores sum_out alone)";
+    const char* needs = " (q and scale are the codes of residual + p: they need the residual; without q, scale and residual the call is the norm alone)";
+    RowOperand ops[6] = {{"x", x, R_IN, "ld_x", ld_x, eb, ""}, {"post_weight", post_weight, R_IN, nullptr, cols, eb, ""}};
+    int n = 2;
+    if (add) ops[n++] = {"residual", residual, R_IN, "ld_r", ld_r, eb, needs};
+    ops[n++] = {"sum_out", sum_out, R_INOUT, "ld_s", ld_s, eb, kSumNote};
+    if (quant) {
+        ops[n++] = {"q", q, R_OUT, "ld_q", ld_q, 1, group};
+        ops[n++] = {"scale", scale, R_OUT, nullptr, rows, 4, group};
+    }
+    const float no_eps = 0.0f;                     // (the shape checks of a norm — cols < 2^24 — without an eps of that name: the only eps here is post_eps)
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, &no_eps, ops, n, &empty, &post_eps); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::olmo_postnorm_add_quant_dispatch<dt>(x, ld_x, post_weight, post_eps, residual, ld_r, sum_out, ld_s, rows, cols, q, ld_q, scale, st); });
+    return check_launch(fn);
+}
+
 int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q,
                                   float* scale, void* h_out, int64_t ld_h, void* stream) {
     Range range_("pq:gelu_mul_quant (K1gg)");

@@ -633,6 +633,71 @@ def gemma_postnorm_add(x: torch.Tensor, post_weight: torch.Tensor, residual: tor
     return summed
 
 
+def olmo_postnorm_add_quantize(x: torch.Tensor, post_weight: torch.Tensor, residual: torch.Tensor, post_eps: float = 1e-6, out: torch.Tensor | None = None):
+    """The post-norm residual flow of OLMo-2 / OLMo-3 in ONE kernel (K1oq): x is a sublayer's output, `post_weight` / `post_eps` the norm on it, `residual` the
+    residual stream; the sum is the input of the next sublayer's int8 projections.  Returns (QTensor, summed), which hold, bit for bit, what this composition gives:
+
+        p      = olmo_rmsnorm(x, post_weight, post_eps)
+        summed = residual + p
+        QT     = quantize(summed)
+
+    (QSPEC NO1-NO5: (x.float() * rsqrt(mean(x.float()²) + eps)) * w.float(), binary32 throughout and ONE storage rounding; PO1: p is never stored; A1; Q1-Q6 on the
+    rows of the sum as stored.)  x and residual have the same shape, dtype and device.  `out` (optional, the same shape and dtype) receives the sum and may be x or
+    residual themselves; any other tensor that overlaps an input is refused.  `summed` has x's shape."""
+    what = "olmo_postnorm_add_quantize"
+    code, x2, r2, rows, cols, summed, s2 = _postnorm_operands(what, x, post_weight, residual, out)
+    if rows == 0 or cols == 0:          # nothing to normalise or add: the empty sum through K1 (scales of empty rows are 1, QSPEC Q3)
+        return quantize(summed), summed
+    pw = post_weight.contiguous()
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_olmo_postnorm_add_quant_rowwise(x2.data_ptr(), L.ld(x2), pw.data_ptr(), float(post_eps), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2), code, rows,
+                                                           cols, q.data_ptr(), cols, scale.data_ptr(), L.stream_ptr(x)), what)
+    return QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape), summed
+
+
+def olmo_postnorm_add(x: torch.Tensor, post_weight: torch.Tensor, residual: torch.Tensor, post_eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:
+    """summed = residual + olmo_rmsnorm(x, post_weight, post_eps) in ONE kernel (K1oa, the form of K1oq without the quantisation: the end of a chain of post-norm-fused
+    layers).  Returns `summed`, the bits of olmo_postnorm_add_quantize's (QSPEC NO1-NO5, PO1, A1).  Arguments and `out` as there."""
+    what = "olmo_postnorm_add"
+    code, x2, r2, rows, cols, summed, s2 = _postnorm_operands(what, x, post_weight, residual, out)
+    if rows == 0 or cols == 0:
+        return summed
+    pw = post_weight.contiguous()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_olmo_postnorm_add_quant_rowwise(x2.data_ptr(), L.ld(x2), pw.data_ptr(), float(post_eps), r2.data_ptr(), L.ld(r2), s2.data_ptr(), L.ld(s2), code, rows,
+                                                           cols, None, 0, None, L.stream_ptr(x)), what)
+    return summed
+
+
+def olmo_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:
+    """(weight * (x.float() * rsqrt(mean(x.float()², -1) + eps))).to(x.dtype) in ONE kernel (K1on, the norm alone: q_norm / k_norm of OLMo-2 / OLMo-3): binary32
+    throughout and ONE storage rounding (QSPEC NO1-NO5: N1-N4's pinned reduction order; spec-exact, and as close to the eager chain as two correctly rounded orders of
+    the same sum are).  x may be a column slice of a wider tensor (the k slice of a fused q/k/v output).  `out` (optional, x's shape and dtype) receives the result and
+    may be x itself; any other tensor that overlaps x is refused.  Returns a tensor of x's shape."""
+    what = "olmo_rmsnorm"
+    L.require_gpu(x, f"{what}(x)")
+    L.require_gpu(weight, f"{what}(weight)")
+    _check_norm_weight(what, x, weight)
+    if out is not None:
+        L.require_gpu(out, f"{what}(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"{what}: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2 = _rows_view(x)
+    rows, cols = x2.shape
+    h = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    h2 = _rows_view_of_out(h, rows, cols, what)
+    if rows == 0 or cols == 0:
+        return h
+    w = weight.contiguous()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_olmo_postnorm_add_quant_rowwise(x2.data_ptr(), L.ld(x2), w.data_ptr(), float(eps), None, 0, h2.data_ptr(), L.ld(h2), code, rows, cols, None, 0, None,
+                                                           L.stream_ptr(x)), what)
+    return h
+
+
 def gelu_mul_quantize(g: torch.Tensor, u: torch.Tensor, kind: str = "gelu_tanh", return_h: bool = False):
     """quantize(F.gelu(g, approximate="tanh") * u, axis=-1) in ONE pass (kernel K1gg): the activation of the down projection of a GeGLU MLP (Gemma's
     down(act_fn(gate(x)) * up(x))) is computed, reduced and encoded in registers.  g and u may be the column halves of one fused gate+up output.  Numerics: QSPEC
