@@ -13,6 +13,9 @@
  *  - every function returns a pq_status; pq_last_error() gives the thread-local message of the last
  *    failing call on this thread.  Nothing throws across the ABI.
  *  - matrices are row-major with explicit leading dimensions in ELEMENTS.
+ *  - the row entries (K1 and its halves, K2, dequant, every K1 fused into a producer or a norm, pq_moe_combine) refuse an output that overlaps another operand —
+ *    PQ_ERR_BAD_ARG before any HIP call, pq_last_error naming both ("q overlaps x") — unless the entry's own comment allows it (sum_out being x or residual).
+ *    Operands that share a leading dimension (column blocks of one buffer) are told apart by their columns, everything else by its bounding byte range.
  *  - dtype codes: 0 = bf16, 1 = fp16, 2 = f32.
  *  - numeric contract: QSPEC v2.  int32 accumulators are exact; float stages are
  *    IEEE binary32, round-to-nearest-even, no contraction, true division.  A NaN in a token row (weight channel)

@@ -244,6 +244,36 @@ bool extents_overlap(const Extent& a, const Extent& b) {
     return true;
 }
 
+// The entries that predate check_row_producer (K1 and its halves, K2, K1s, K1g, K1n, dequant, moe_combine) keep their own shape checks and messages; their kernels carry
+// __restrict__ on every operand, so an output that overlaps anything else is refused here, by name, before any HIP call.  `v`: the operands in the order of the
+// argument list, inputs first; null operands (a nullable h_out) are skipped by extents_overlap.
+struct NamedExtent {
+    const char* name;
+    Extent e;
+    bool out;
+};
+Extent vec_extent(const void* p, int64_t n, int64_t elem_bytes) { return extent_of(p, n, 1, n, elem_bytes); }
+int32_t check_disjoint(const char* fn, const NamedExtent* v, int n) {
+    for (int o = 0; o < n; ++o) {
+        if (!v[o].out) continue;
+        for (int j = 0; j < n; ++j)
+            if (j != o && (!v[j].out || j > o) && extents_overlap(v[o].e, v[j].e)) return fail(PQ_ERR_BAD_ARG, "%s: %s overlaps %s", fn, v[o].name, v[j].name);
+    }
+    return PQ_OK;
+}
+
+int64_t dtype_bytes(int32_t dtype) { return dtype == PQ_F32 ? 4 : 2; }
+// g, u (u null: a one-input entry), the amax vector of the split halves (an output of the first half, an input of the second), q / scale / h_out (each nullable)
+int32_t check_gated_disjoint(const char* fn, const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, const void* amax_bits,
+                             bool amax_is_out, const void* q, int64_t ld_q, const void* scale, const void* h_out, int64_t ld_h) {
+    if (cols == 0) return PQ_OK;
+    const int64_t eb = dtype_bytes(dtype);
+    const NamedExtent ops[] = {{u ? "g" : "x", extent_of(g, ld_g, rows, cols, eb), false}, {"u", extent_of(u, ld_u, rows, cols, eb), false},
+                               {"amax_bits", vec_extent(amax_bits, rows, 4), amax_is_out},  {"q", extent_of(q, ld_q, rows, cols, 1), true},
+                               {"scale", vec_extent(scale, rows, 4), true},                 {"h_out", extent_of(h_out, ld_h, rows, cols, eb), true}};
+    return check_disjoint(fn, ops, 6);
+}
+
 enum Role { R_IN, R_INOUT, R_OUT };
 struct RowOperand {
     const char* name;
@@ -328,6 +358,10 @@ int32_t pq_quant_rowwise(const void* x, int32_t dtype, int64_t rows, int64_t col
     if (bad_mat(x, rows, cols, ld_x) || bad_mat(q, rows, cols, ld_q) || (rows > 0 && !scale))
         return fail(PQ_ERR_BAD_ARG, "pq_quant_rowwise: bad matrix (rows=%lld cols=%lld ld_x=%lld ld_q=%lld)", (long long)rows, (long long)cols, (long long)ld_x, (long long)ld_q);
     if (rows == 0) return PQ_OK;
+    if (cols > 0) {
+        const NamedExtent ops[] = {{"x", extent_of(x, ld_x, rows, cols, dtype_bytes(dtype)), false}, {"q", extent_of(q, ld_q, rows, cols, 1), true}, {"scale", vec_extent(scale, rows, 4), true}};
+        if (const int32_t rc = check_disjoint("pq_quant_rowwise", ops, 3)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::quant_rowwise_dispatch<dt>(x, rows, cols, ld_x, q, ld_q, scale, st); });
     return check_launch("pq_quant_rowwise");
@@ -340,6 +374,10 @@ int32_t pq_quant_colwise(const void* x, int32_t dtype, int64_t rows, int64_t col
     if (bad_mat(x, rows, cols, ld_x) || bad_mat(q, rows, cols, ld_q) || (cols > 0 && !scale))
         return fail(PQ_ERR_BAD_ARG, "pq_quant_colwise: bad matrix (rows=%lld cols=%lld ld_x=%lld ld_q=%lld)", (long long)rows, (long long)cols, (long long)ld_x, (long long)ld_q);
     if (cols == 0) return PQ_OK;
+    if (rows > 0) {
+        const NamedExtent ops[] = {{"x", extent_of(x, ld_x, rows, cols, dtype_bytes(dtype)), false}, {"q", extent_of(q, ld_q, rows, cols, 1), true}, {"scale", vec_extent(scale, cols, 4), true}};
+        if (const int32_t rc = check_disjoint("pq_quant_colwise", ops, 3)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const hipError_t e = by_dtype(dtype, [&](auto dt) { return pq::quant_colwise_dispatch<dt>(x, rows, cols, ld_x, q, ld_q, scale, st); });
     if (e != hipSuccess) return fail(PQ_ERR_LAUNCH, "pq_quant_colwise: initialising the amax scratch: %s", hipGetErrorString(e));
@@ -354,6 +392,7 @@ int32_t pq_silu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, in
         (h_out && ld_h < cols))
         return fail(PQ_ERR_BAD_ARG, "pq_silu_mul_quant_rowwise: bad matrix (rows=%lld cols=%lld ld_g=%lld ld_u=%lld ld_q=%lld ld_h=%lld)", (long long)rows, (long long)cols, (long long)ld_g, (long long)ld_u, (long long)ld_q, (long long)ld_h);
     if (rows == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_silu_mul_quant_rowwise", g, ld_g, u, ld_u, dtype, rows, cols, nullptr, false, q, ld_q, scale, h_out, ld_h)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::silu_mul_quant_dispatch<dt>(g, ld_g, u, ld_u, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
     return check_launch("pq_silu_mul_quant_rowwise");
@@ -377,6 +416,7 @@ int32_t pq_glu_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t
     if (bad_mat(g, rows, cols, ld_g) || bad_mat(u, rows, cols, ld_u) || bad_mat(q, rows, cols, ld_q) || (rows > 0 && !scale) || (h_out && ld_h < cols))
         return fail(PQ_ERR_BAD_ARG, "pq_glu_quant_rowwise: bad matrix (rows=%lld cols=%lld ld_g=%lld ld_u=%lld ld_q=%lld ld_h=%lld)", (long long)rows, (long long)cols, (long long)ld_g, (long long)ld_u, (long long)ld_q, (long long)ld_h);
     if (rows == 0 || cols == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_glu_quant_rowwise", g, ld_g, u, ld_u, dtype, rows, cols, nullptr, false, q, ld_q, scale, h_out, ld_h)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::glu_quant_dispatch<dt>(kind, g, ld_g, u, ld_u, rows, cols, limit, alpha, q, ld_q, scale, h_out, ld_h, st); });
     return check_launch("pq_glu_quant_rowwise");
@@ -389,6 +429,7 @@ int32_t pq_silu_mul_rowamax(const void* g, int64_t ld_g, const void* u, int64_t 
     if (bad_mat(g, rows, cols, ld_g) || bad_mat(u, rows, cols, ld_u) || (rows > 0 && !amax_bits))
         return fail(PQ_ERR_BAD_ARG, "pq_silu_mul_rowamax: bad matrix (rows=%lld cols=%lld ld_g=%lld ld_u=%lld)", (long long)rows, (long long)cols, (long long)ld_g, (long long)ld_u);
     if (rows == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_silu_mul_rowamax", g, ld_g, u, ld_u, dtype, rows, cols, amax_bits, true, nullptr, 0, nullptr, nullptr, 0)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::silu_mul_split_dispatch<dt, 1, false>(g, ld_g, u, ld_u, rows, cols, amax_bits, nullptr, 0, nullptr, st); });
     return check_launch("pq_silu_mul_rowamax");
@@ -401,6 +442,7 @@ int32_t pq_silu_mul_quant_rowwise_amax(const void* g, int64_t ld_g, const void* 
     if (bad_mat(g, rows, cols, ld_g) || bad_mat(u, rows, cols, ld_u) || bad_mat(q, rows, cols, ld_q) || (rows > 0 && (!scale || !amax_bits)))
         return fail(PQ_ERR_BAD_ARG, "pq_silu_mul_quant_rowwise_amax: bad matrix (rows=%lld cols=%lld ld_g=%lld ld_u=%lld ld_q=%lld)", (long long)rows, (long long)cols, (long long)ld_g, (long long)ld_u, (long long)ld_q);
     if (rows == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_silu_mul_quant_rowwise_amax", g, ld_g, u, ld_u, dtype, rows, cols, amax_bits, false, q, ld_q, scale, nullptr, 0)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* ab = const_cast<uint32_t*>(amax_bits);          // (read-only in this mode)
     by_dtype(dtype, [&](auto dt) { pq::silu_mul_split_dispatch<dt, 2, false>(g, ld_g, u, ld_u, rows, cols, ab, q, ld_q, scale, st); });
@@ -413,6 +455,7 @@ int32_t pq_quant_rowamax(const void* x, int32_t dtype, int64_t rows, int64_t col
     if (bad_mat(x, rows, cols, ld_x) || (rows > 0 && !amax_bits))
         return fail(PQ_ERR_BAD_ARG, "pq_quant_rowamax: bad matrix (rows=%lld cols=%lld ld_x=%lld)", (long long)rows, (long long)cols, (long long)ld_x);
     if (rows == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_quant_rowamax", x, ld_x, nullptr, 0, dtype, rows, cols, amax_bits, true, nullptr, 0, nullptr, nullptr, 0)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::silu_mul_split_dispatch<dt, 1, true>(x, ld_x, nullptr, 0, rows, cols, amax_bits, nullptr, 0, nullptr, st); });
     return check_launch("pq_quant_rowamax");
@@ -425,6 +468,7 @@ int32_t pq_quant_rowwise_amax(const void* x, int32_t dtype, int64_t rows, int64_
     if (bad_mat(x, rows, cols, ld_x) || bad_mat(q, rows, cols, ld_q) || (rows > 0 && (!scale || !amax_bits)))
         return fail(PQ_ERR_BAD_ARG, "pq_quant_rowwise_amax: bad matrix (rows=%lld cols=%lld ld_x=%lld ld_q=%lld)", (long long)rows, (long long)cols, (long long)ld_x, (long long)ld_q);
     if (rows == 0) return PQ_OK;
+    if (const int32_t rc = check_gated_disjoint("pq_quant_rowwise_amax", x, ld_x, nullptr, 0, dtype, rows, cols, amax_bits, false, q, ld_q, scale, nullptr, 0)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* ab = const_cast<uint32_t*>(amax_bits);          // (read-only in this mode)
     by_dtype(dtype, [&](auto dt) { pq::silu_mul_split_dispatch<dt, 2, true>(x, ld_x, nullptr, 0, rows, cols, ab, q, ld_q, scale, st); });
@@ -439,6 +483,12 @@ int32_t pq_rmsnorm_quant_rowwise(const void* x, int64_t ld_x, const void* weight
         (h_out && ld_h < cols) || cols >= (1 << 24) || !(eps >= 0.0f))
         return fail(PQ_ERR_BAD_ARG, "pq_rmsnorm_quant_rowwise: bad arguments (rows=%lld cols=%lld ld_x=%lld ld_q=%lld ld_h=%lld eps=%g)", (long long)rows, (long long)cols, (long long)ld_x, (long long)ld_q, (long long)ld_h, (double)eps);
     if (rows == 0) return PQ_OK;
+    if (cols > 0) {
+        const int64_t eb = dtype_bytes(dtype);
+        const NamedExtent ops[] = {{"x", extent_of(x, ld_x, rows, cols, eb), false}, {"weight", vec_extent(weight, cols, eb), false}, {"q", extent_of(q, ld_q, rows, cols, 1), true},
+                                   {"scale", vec_extent(scale, rows, 4), true}, {"h_out", extent_of(h_out, ld_h, rows, cols, eb), true}};
+        if (const int32_t rc = check_disjoint("pq_rmsnorm_quant_rowwise", ops, 5)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (cols == 0) pq::quant_rowwise_dispatch<PQ_F32>(x, rows, 0, 1, q, 1, scale, st);       // nothing to normalise: scale = 1 (QSPEC Q3), no codes
     else by_dtype(dtype, [&](auto dt) { pq::rmsnorm_quant_dispatch<dt>(x, ld_x, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st); });
@@ -666,6 +716,11 @@ int32_t pq_dequant(const int8_t* q, int64_t ld_q, const float* scale, int32_t ax
     if (bad_mat(q, rows, cols, ld_q) || bad_mat(out, rows, cols, ld_out) || (rows > 0 && cols > 0 && !scale))
         return fail(PQ_ERR_BAD_ARG, "pq_dequant: bad matrix (rows=%lld cols=%lld)", (long long)rows, (long long)cols);
     if (rows == 0 || cols == 0) return PQ_OK;
+    {
+        const NamedExtent ops[] = {{"q", extent_of(q, ld_q, rows, cols, 1), false}, {"scale", vec_extent(scale, axis == 0 ? cols : rows, 4), false},
+                                   {"out", extent_of(out, ld_out, rows, cols, dtype_bytes(out_dtype)), true}};
+        if (const int32_t rc = check_disjoint("pq_dequant", ops, 3)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(out_dtype, [&](auto dt) { pq::dequant_dispatch<dt>(q, ld_q, scale, axis, rows, cols, out, ld_out, st); });
     return check_launch("pq_dequant");
@@ -993,6 +1048,12 @@ int32_t pq_moe_combine(const void* y, int64_t ldy, int32_t dtype, int64_t M_tota
             return fail(PQ_ERR_BAD_ALIGN, "%s: y, out and topk_w must be aligned to their element size", what);
     }
     if (T == 0 || H == 0) return PQ_OK;
+    {
+        const int64_t eb = dtype_bytes(dtype);
+        const NamedExtent ops[] = {{"y", extent_of(y, ldy, M_total, H, eb), false}, {"rows_of", vec_extent(rows_of, T * k, 4), false}, {"slot_of", vec_extent(slot_of, T * k, 4), false},
+                                   {"topk_w", extent_of(topk_w, ld_w, T, k, eb), false}, {"out", extent_of(out, ld_out, T, H, eb), true}};
+        if (const int32_t rc = check_disjoint(what, ops, 5)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto dt) { pq::moe_combine_dispatch<dt>(y, ldy, M_total, rows_of, slot_of, topk_w, ld_w, T, k, H, out, ld_out, st); });
     return check_launch(what);

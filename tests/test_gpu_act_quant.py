@@ -2,7 +2,7 @@
 compared bit for bit (NaNs as a class) with the CPU specification (tests/act_spec.py: QSPEC U1-U3, then Q1-Q6 by oracle.qspec_numpy), over a grid that launches
 every instantiation: one wave per row at 1 / 2 / 4 vectors, 512 threads x 3 vectors (and the same rows with PQ_SILU_TPR=256), 256 threads per row at 1 .. 16
 vectors, the generic kernel on ragged widths, unaligned bases and odd leading dimensions, column blocks of a wider tensor; EVERY 16-bit pattern through the vector
-and the generic kernel; rows on and off the fast-division domain of the tanh GELU; guarded margins around every output.  Addressing past 2^31 elements is not covered."""
+and the generic kernel; rows on and off the fast-division domain of the tanh GELU; guarded margins around every output.  Addressing past 2^31 elements and more than 4 x 65 535 rows: tests/test_gpu_row_addressing.py."""
 import numpy as np
 import pytest
 import torch

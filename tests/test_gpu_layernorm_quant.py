@@ -2,7 +2,7 @@
 (NaNs as a class) with the CPU specification (tests/lnorm_spec.py: QSPEC L1-L6, then Q1-Q6 by oracle.qspec_numpy), over a grid that launches every instantiation:
 one wave per row at 1 / 2 / 4 vectors (8 with PQ_RMS_WAVE_MAX=512), 256 threads per row at 1 .. 16 vectors (and on short rows with PQ_RMS_WAVE_MAX=0), the generic
 kernel on ragged widths, unaligned bases and odd leading dimensions; with and without bias; rows of zeros, constant rows, NaN / Inf rows; guarded margins around every
-output.  Addressing past 2^31 elements is NOT covered here (a 2^31-element bf16 operand plus its codes does not fit next to the suite's other tests)."""
+output.  Addressing past 2^31 elements and more than 4 x 65 535 rows: tests/test_gpu_row_addressing.py."""
 import numpy as np
 import pytest
 import torch
