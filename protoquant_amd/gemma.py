@@ -27,9 +27,10 @@ import torch
 from torch import nn
 
 from .gptlike import activation_kind, fusable_norms
-from .llama import RMSNormQuant, _FusedSlice, _HandOver, _ProbeLayer, _forward_extra_params, _fuse_residual, _link_chain, fuse_llama_layers
+from .llama import RMSNormQuant, _FusedSlice, _fuse_residual, fuse_llama_layers
 from .qlinear import FusedQLinear, GatedMLP, qlinear
 from .qtensor import add_gemma_rmsnorm_quantize, gemma_postnorm_add, gemma_postnorm_add_rmsnorm_quantize, gemma_rmsnorm_quantize
+from .residual_flow import NamedFusedLayer, _forward_extra_params, _hooked, _ProbeLayer, attention, fuse_stacks, probe_named_flow
 
 
 class GemmaRMSNormQuant(RMSNormQuant):
@@ -120,23 +121,9 @@ def is_gemma_rmsnorm(m) -> bool:
 
 
 # ---------------------------------------------------------------- is it a GeGLU MLP?  (by behaviour)
-class _MLPStandin:
-    """Stand-in for `self` in an MLP class's own forward: the three projections and the activation are exact functions on small integers; any other submodule is
-    a refusal; every other attribute is the real module's."""
-
-    def __init__(self, mlp, children):
-        self.__dict__["_mlp"] = mlp
-        self.__dict__.update(children)
-
-    def __getattr__(self, name):
-        v = getattr(self.__dict__["_mlp"], name)
-        if isinstance(v, nn.Module):
-            raise RuntimeError(f"forward reads the submodule {name!r}")
-        return v
-
-
 def _mlp_flow_is_gated(mlp: nn.Module) -> bool:
-    """True iff type(mlp).forward IS down_proj(act_fn(gate_proj(x)) * up_proj(x)), each child called once: probed with exact functions, not pattern-matched."""
+    """True iff type(mlp).forward IS down_proj(act_fn(gate_proj(x)) * up_proj(x)), each child called once: probed with exact functions on small integers in the
+    children's places (any other submodule is a refusal, every other attribute is the real module's), not pattern-matched."""
     calls = {"gate_proj": 0, "up_proj": 0, "down_proj": 0, "act_fn": 0}
 
     def counted(name, f):
@@ -150,7 +137,7 @@ def _mlp_flow_is_gated(mlp: nn.Module) -> bool:
     x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)
     try:
         with torch.no_grad():
-            out = type(mlp).forward(_MLPStandin(mlp, kids), x.clone())
+            out = type(mlp).forward(_ProbeLayer(mlp, kids), x.clone())
     except Exception:          # noqa: BLE001
         return False
     want = (x * 2.0) ** 2 * (x + 1.0) - 3.0
@@ -220,7 +207,13 @@ def fuse_gemma_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
 
 
 # ---------------------------------------------------------------- the sandwich residual flow of Gemma-2 / Gemma-3 (opt-in)
-_SANDWICH = ("input_layernorm", "self_attn", "post_attention_layernorm", "pre_feedforward_layernorm", "mlp", "post_feedforward_layernorm")
+_SANDWICH = {"input_layernorm": lambda t: t * 2.0, "self_attn": attention(lambda h: h + 1.0), "post_attention_layernorm": lambda t: t * 3.0 - 1.0,
+             "pre_feedforward_layernorm": lambda t: t * 0.5 - 3.0, "mlp": lambda t: t * t, "post_feedforward_layernorm": lambda t: t * 4.0 + 5.0}
+
+
+def _sandwich_flow(x):
+    r1 = x + ((x * 2.0 + 1.0) * 3.0 - 1.0)
+    return r1 + ((r1 * 0.5 - 3.0) ** 2 * 4.0 + 5.0)
 
 
 def residual_flow_is_sandwich(layer: nn.Module, cls=None) -> bool:
@@ -234,50 +227,10 @@ def residual_flow_is_sandwich(layer: nn.Module, cls=None) -> bool:
     returned.  Probed like llama.residual_flow_is_llama, not pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a
     tiny CPU tensor, and its result must EQUAL the formula.  transformers' Gemma2DecoderLayer and Gemma3DecoderLayer pass; Gemma v1 and Llama (no post-norms),
     OLMo-2 (post-norms only), Gemma-3n (further submodules) and any forward that raises on the stand-in do not."""
-    cls = cls or type(layer)
-    try:
-        names, var_kw = _forward_extra_params(cls)
-    except (TypeError, ValueError, AttributeError):
-        return False
-    given = {n: object() for n in names}
-    if var_kw:
-        given["pq_probe_extra"] = object()
-    calls = {c: 0 for c in _SANDWICH}
-    seen = {}
-
-    def counted(name, f):
-        def run(t):
-            calls[name] += 1
-            return f(t)
-        return run
-
-    def attn(*a, **kw):          # (SandwichFusedLayer calls self_attn(hidden_states=h, **kwargs): that form and no other is accepted)
-        calls["self_attn"] += 1
-        h = kw.pop("hidden_states")
-        seen["positional"], seen["kwargs"] = len(a), kw
-        return h + 1.0, None
-
-    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
-    probe = _ProbeLayer(layer, {"input_layernorm": counted("input_layernorm", lambda t: t * 2.0), "self_attn": attn,
-                                "post_attention_layernorm": counted("post_attention_layernorm", lambda t: t * 3.0 - 1.0),
-                                "pre_feedforward_layernorm": counted("pre_feedforward_layernorm", lambda t: t * 0.5 - 3.0), "mlp": counted("mlp", lambda t: t * t),
-                                "post_feedforward_layernorm": counted("post_feedforward_layernorm", lambda t: t * 4.0 + 5.0)})
-    try:
-        with torch.no_grad():
-            out = cls.forward(probe, x.clone(), **given)
-    except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
-        return False
-    if not isinstance(out, torch.Tensor) or any(n != 1 for n in calls.values()):
-        return False
-    kw = seen["kwargs"]
-    if seen["positional"] != 0 or set(kw) != set(given) or any(kw[k] is not given[k] for k in given):
-        return False
-    r1 = x + ((x * 2.0 + 1.0) * 3.0 - 1.0)
-    want = r1 + ((r1 * 0.5 - 3.0) ** 2 * 4.0 + 5.0)
-    return out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+    return probe_named_flow(layer, cls or type(layer), _SANDWICH, _sandwich_flow)
 
 
-class SandwichFusedLayer(nn.Module):
+class SandwichFusedLayer(NamedFusedLayer):
     """A sandwich-flow decoder layer (Gemma-2, Gemma-3) whose two post-norms and residual adds run inside the norm + quantisation kernels that follow them (K1pang,
     gemma_postnorm_add_rmsnorm_quantize; K1pa, gemma_postnorm_add, at the end of a chain):
 
@@ -294,13 +247,11 @@ class SandwichFusedLayer(nn.Module):
     from its original class: the object, its children under their names, its other attributes, its hooks and every isinstance check on it stay as they were.  The
     tensor the layer was called with is never written; the hand-over is consumed at the next layer's entry and never served for another tensor or a tensor changed in
     place since."""
-    _pq_residual_fused = True
+    _pq_prefix, _pq_residual_fused = "SandwichFused", True
 
     def forward(self, hidden_states, *args, **kwargs):
-        if args:          # positional arguments of the original forward, by its own parameter names
-            if len(args) > len(self._rf_argnames):
-                raise TypeError(f"{type(self).__name__}.forward takes at most {len(self._rf_argnames) + 1} positional arguments")
-            kwargs.update(zip(self._rf_argnames, args))
+        if args:
+            self._fold_positional(args, kwargs)
         h = self._rf_inbox.take(hidden_states)
         if h is None:
             h = self.input_layernorm(hidden_states)
@@ -316,19 +267,6 @@ class SandwichFusedLayer(nn.Module):
         return out
 
 
-_SF_CLASSES: dict = {}
-
-
-def _sandwich_fused_class(cls):
-    if cls not in _SF_CLASSES:
-        _SF_CLASSES[cls] = type("SandwichFused" + cls.__name__, (SandwichFusedLayer, cls), {"__doc__": SandwichFusedLayer.__doc__})
-    return _SF_CLASSES[cls]
-
-
-def _hooked(m: nn.Module) -> bool:
-    return bool(m._forward_hooks) or bool(m._forward_pre_hooks)
-
-
 def fuse_gemma_postnorm_residual(model: nn.Module) -> int:
     """Opt-in, after fuse_gemma_layers(model) (which it leaves exactly as it was: a separate entry, so nothing changes for a caller who does not ask): every layer
     of a ModuleList becomes a SandwichFusedLayer (in place) if ALL of these hold — it has the six children input_layernorm, self_attn, post_attention_layernorm,
@@ -340,29 +278,19 @@ def fuse_gemma_postnorm_residual(model: nn.Module) -> int:
     the eager chain, so the model's bits change against the model without this switch.  The module that owns the ModuleList gets an always-called forward hook that
     drops every pending hand-over when its forward ends.  Returns the number of layers changed by THIS call (a second call finds nothing left to change and returns
     0); llama.residual_fused_layers(model) counts them over all calls."""
-    n = 0
-    for owner in list(model.modules()):
-        for _, stack in list(owner.named_children()):
-            if not isinstance(stack, nn.ModuleList):
-                continue
-            fresh = []
-            for layer in stack:
-                if isinstance(layer, SandwichFusedLayer) or not all(hasattr(layer, c) for c in _SANDWICH):
-                    continue
-                n1, n2 = layer.input_layernorm, layer.pre_feedforward_layernorm
-                if not (isinstance(n1, GemmaRMSNormQuant) and isinstance(n2, GemmaRMSNormQuant)) or n1.weight.shape != n2.weight.shape:
-                    continue
-                posts = (layer.post_attention_layernorm, layer.post_feedforward_layernorm)
-                if not all(is_gemma_rmsnorm(p) and p.weight.shape == n1.weight.shape and not _hooked(p) for p in posts):
-                    continue
-                cls = type(layer)
-                if not residual_flow_is_sandwich(layer, cls):
-                    continue
-                n1.__class__ = n2.__class__ = GemmaSandwichNormQuant          # (the same objects: they learn the post_norm argument)
-                layer._rf_argnames = _forward_extra_params(cls)[0]
-                layer._rf_inbox, layer._rf_next = _HandOver(), [None]
-                layer.__class__ = _sandwich_fused_class(cls)
-                fresh.append(layer)
-            _link_chain(owner, stack, fresh, SandwichFusedLayer)          # (a chain that ends, ends with K1pa)
-            n += len(fresh)
-    return n
+    def convert(layer):
+        if isinstance(layer, SandwichFusedLayer) or not all(hasattr(layer, c) for c in _SANDWICH):
+            return None
+        n1, n2 = layer.input_layernorm, layer.pre_feedforward_layernorm
+        if not (isinstance(n1, GemmaRMSNormQuant) and isinstance(n2, GemmaRMSNormQuant)) or n1.weight.shape != n2.weight.shape:
+            return None
+        posts = (layer.post_attention_layernorm, layer.post_feedforward_layernorm)
+        if not all(is_gemma_rmsnorm(p) and p.weight.shape == n1.weight.shape and not _hooked(p) for p in posts):
+            return None
+        cls = type(layer)
+        if not residual_flow_is_sandwich(layer, cls):
+            return None
+        n1.__class__ = n2.__class__ = GemmaSandwichNormQuant          # (the same objects: they learn the post_norm argument)
+        layer._rf_argnames = _forward_extra_params(cls)[0]
+        return cls
+    return fuse_stacks(model, SandwichFusedLayer, convert)          # (a chain that ends, ends with K1pa)

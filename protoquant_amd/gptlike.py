@@ -27,9 +27,10 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .llama import _FusedSlice, _HandOver, _link_chain, _rf_clear_hook
+from .llama import _FusedSlice
 from .qlinear import FusedQLinear, qlinear
 from .qtensor import act_quantize, add2_layernorm_quantize, add_layernorm_quantize, layernorm_quantize, layernorm_quantize2
+from .residual_flow import _H, FlowPlan, FusedLayer, _hooked, _ProbeRefused, fuse_stacks
 
 
 class LayerNormQuant(nn.Module):
@@ -105,10 +106,6 @@ def activation_kind(act) -> str | None:
 
 
 # ---------------------------------------------------------------- the probe
-class _ProbeRefused(Exception):
-    pass
-
-
 class _Probed:
     """What a fused norm or activation returns under the probe: the metadata surface of a per-token QTensor (shape, device) and nothing else.  Any other attribute
     is a refusal; arithmetic and torch functions fail on it by themselves."""
@@ -295,23 +292,16 @@ def fusable_activation(mlp: nn.Module):
 
 
 # ---------------------------------------------------------------- the residual adds fused into the norms that follow them (opt-in)
-_H = "pq:norm-output"          # the place of the first norm's output in the recorded attention call
 _CONSTANTS = (type(None), bool, int, float, str)
 
 
-class ResidualPlan:
-    """What the probe of a block class's forward recorded (residual_flow_plan): the names of the four roles, the attention call to replay — for every positional
-    and keyword argument either _H, ("param", name of the block's own parameter handed on) or ("const", value) — whether the block's **kwargs go to the attention,
-    the block parameters the attention never saw (`withheld`: a call that sets one of them runs the original forward) and the stateless children (dropouts) that
-    the eval-mode probe found to be no-ops on the stream (a call in training mode runs the original forward)."""
+class ResidualPlan(FlowPlan):
+    """What the probe of a block class's forward recorded (residual_flow_plan): the names of the four roles, and the replay of the attention call, the withheld
+    parameters, the defaults and the stateless children of a FlowPlan."""
 
-    def __init__(self, cls, n1, attn, n2, mlp, args, kwargs, var_kw, withheld, defaults, stateless):
-        self.cls, self.n1, self.attn, self.n2, self.mlp = cls, n1, attn, n2, mlp
-        self.args, self.kwargs, self.var_kw, self.withheld, self.defaults, self.stateless = tuple(args), dict(kwargs), var_kw, tuple(withheld), dict(defaults), tuple(stateless)
-        self.signature = inspect.signature(cls.forward)
-        ps = list(self.signature.parameters.values())
-        self.first = ps[1].name
-        self.var_kw_name = next((p.name for p in ps if p.kind == p.VAR_KEYWORD), None)
+    def __init__(self, cls, n1, attn, n2, mlp, *replay):
+        super().__init__(cls, *replay)
+        self.n1, self.attn, self.n2, self.mlp = n1, attn, n2, mlp
 
 
 class _ProbeBlock:
@@ -505,7 +495,7 @@ def _probe_flow(block, cls, norm_names, probe_once, attn_input, roles):
     return run, run2, args, kwargs, forwards_extra, withheld, defaults, given1
 
 
-class ResidualFusedBlock(nn.Module):
+class ResidualFusedBlock(FusedLayer):
     """A sequential pre-norm decoder block whose two residual adds run inside the LayerNorm + quantisation kernels that follow them (K1al, add_layernorm_quantize):
 
         h          = the QTensor handed over for this very tensor, else N1(hidden)
@@ -521,24 +511,18 @@ class ResidualFusedBlock(nn.Module):
     called with is never written; the hand-over is consumed at the next block's entry and never served for another tensor or a tensor changed in place since.
     Whatever the probe did not see — an argument the attention never receives set to something else than its default (GPT-2's encoder_hidden_states), training
     mode with a dropout on the stream — runs the original class's forward for that call."""
-    _pq_residual_fused = True
+    _pq_prefix, _pq_residual_fused = "ResidualFused", True
 
     def forward(self, *args, **kwargs):
         plan = self._rfb_plan
-        bound = plan.signature.bind(self, *args, **kwargs)          # (a TypeError here is the one the original forward would raise)
-        bound.apply_defaults()
-        given = bound.arguments
-        extras = given.get(plan.var_kw_name, {}) if plan.var_kw_name else {}
+        given, extras, out = plan.bind(self, args, kwargs)
+        if given is None:          # (a call the probe did not cover: the original forward ran)
+            return out
         hidden = given[plan.first]
-        if ((self.training and plan.stateless) or not isinstance(hidden, torch.Tensor) or (extras and not plan.var_kw)
-                or any(given[n] is not plan.defaults[n] for n in plan.withheld)):
-            self._rf_inbox.clear()
-            return plan.cls.forward(self, *args, **kwargs)
         h = self._rf_inbox.take(hidden)
         if h is None:
             h = getattr(self, plan.n1)(hidden)
-        value = lambda e: h if e == _H else given[e[1]] if e[0] == "param" else e[1]          # noqa: E731
-        attn_out = getattr(self, plan.attn)(*(value(e) for e in plan.args), **{k: value(e) for k, e in plan.kwargs.items()}, **extras)[0]
+        attn_out = plan.replay(self, h, given, extras)[0]
         hq, resid = getattr(self, plan.n2)(attn_out, residual=hidden)
         m = getattr(self, plan.mlp)(hq)
         nxt = self._rf_next[0]
@@ -548,23 +532,6 @@ class ResidualFusedBlock(nn.Module):
         nxt._rf_inbox.put(out, hq2)
         return out
 
-    def __reduce_ex__(self, protocol):          # (the class is made at run time: a copy — deep or pickled — makes it again from the original class)
-        return _rebuild_fused_block, (self._rfb_plan.cls,), self.__dict__
-
-
-_RFB_CLASSES: dict = {}
-
-
-def _residual_fused_block_class(cls):
-    if cls not in _RFB_CLASSES:
-        _RFB_CLASSES[cls] = type("ResidualFused" + cls.__name__, (ResidualFusedBlock, cls), {"__doc__": ResidualFusedBlock.__doc__})
-    return _RFB_CLASSES[cls]
-
-
-def _rebuild_fused_block(cls):
-    fused = _residual_fused_block_class(cls)
-    return fused.__new__(fused)
-
 
 def fuse_layernorm_residual(model: nn.Module) -> int:
     """Opt-in, after fuse_layernorm_layers (which it leaves exactly as it was: a separate entry, so nothing changes for a caller who does not ask): every block of a
@@ -572,34 +539,15 @@ def fuse_layernorm_residual(model: nn.Module) -> int:
     block keeps the fusions it has and breaks the chain (its predecessor ends with a torch add); the model's final norm is not touched.  The module that owns the
     ModuleList gets an always-called forward hook that drops every pending hand-over when its forward ends.  Returns the number of blocks changed by THIS call (a
     second call finds nothing left to change); residual_fused_blocks(model) counts them over all calls.  Composes with fuse_llama_layers in any order."""
-    n = 0
-    for owner in list(model.modules()):
-        for _, stack in list(owner.named_children()):
-            if not isinstance(stack, nn.ModuleList):
-                continue
-            fresh = []
-            for block in stack:
-                if isinstance(block, ResidualFusedBlock) or getattr(type(block), "_pq_residual_fused", False):
-                    continue
-                plan = residual_flow_plan(block)
-                if plan is None:
-                    continue
-                block._rfb_plan = plan
-                block._rf_inbox, block._rf_next = _HandOver(), [None]
-                block.__class__ = _residual_fused_block_class(plan.cls)
-                fresh.append(block)
-            # (re)link the chain: a block hands over to its successor in the stack when that one is residual-fused too; anything else ends the chain with a torch add
-            for i, block in enumerate(stack):
-                if isinstance(block, ResidualFusedBlock):
-                    nxt = stack[i + 1] if i + 1 < len(stack) else None
-                    block._rf_next = [nxt if isinstance(nxt, ResidualFusedBlock) else None]          # (a list: the next block is registered once, in the stack)
-            if fresh:
-                if not hasattr(owner, "_rf_layers"):
-                    owner._rf_layers = []
-                    owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
-                owner._rf_layers.extend(fresh)
-                n += len(fresh)
-    return n
+    def convert(block):
+        if getattr(type(block), "_pq_residual_fused", False):
+            return None
+        plan = residual_flow_plan(block)
+        if plan is None:
+            return None
+        block._rfb_plan = plan
+        return plan.cls
+    return fuse_stacks(model, ResidualFusedBlock, convert)          # (a chain that ends, ends with a torch add)
 
 
 def residual_fused_blocks(model: nn.Module) -> int:
@@ -655,19 +603,15 @@ def _rounding_operands():
 _PAIRS = (("x", "a", "m"), ("a", "m", "x"), ("x", "m", "a"))          # (the pair added first, then the third operand)
 
 
-class ParallelPlan:
+class ParallelPlan(FlowPlan):
     """What the probe of a block class's forward recorded (parallel_flow_plan): the attention and the MLP, the norm each of them reads (the same one in a block with
     a single norm), `order` — the operands of the three-way sum ("x": the block's input, "a": the attention's output, "m": the MLP's) with the pair that the block
-    adds FIRST in front — and the replay of the attention call, the withheld parameters, the defaults and the stateless children as in ResidualPlan."""
+    adds FIRST in front — and the replay of the attention call, the withheld parameters, the defaults and the stateless children of a FlowPlan."""
 
-    def __init__(self, cls, attn, mlp, attn_norm, mlp_norm, order, args, kwargs, var_kw, withheld, defaults, stateless):
-        self.cls, self.attn, self.mlp, self.attn_norm, self.mlp_norm, self.order = cls, attn, mlp, attn_norm, mlp_norm, tuple(order)
+    def __init__(self, cls, attn, mlp, attn_norm, mlp_norm, order, *replay):
+        super().__init__(cls, *replay)
+        self.attn, self.mlp, self.attn_norm, self.mlp_norm, self.order = attn, mlp, attn_norm, mlp_norm, tuple(order)
         self.norms = (attn_norm,) if attn_norm == mlp_norm else (attn_norm, mlp_norm)
-        self.args, self.kwargs, self.var_kw, self.withheld, self.defaults, self.stateless = tuple(args), dict(kwargs), var_kw, tuple(withheld), dict(defaults), tuple(stateless)
-        self.signature = inspect.signature(cls.forward)
-        ps = list(self.signature.parameters.values())
-        self.first = ps[1].name
-        self.var_kw_name = next((p.name for p in ps if p.kind == p.VAR_KEYWORD), None)
 
 
 class _ParallelRun:
@@ -739,10 +683,6 @@ def _probe_parallel_once(block, cls, norm_names, given, poison=False, fixed=None
     return run, torch.equal(out, want)
 
 
-def _norm_is_hooked(m: nn.Module) -> bool:
-    return bool(m._forward_hooks or m._forward_pre_hooks)
-
-
 def parallel_flow_plan(block: nn.Module, cls=None):
     """A ParallelPlan iff `cls.forward` (default: the block's own class) IS the parallel-residual data flow on this block:
 
@@ -758,7 +698,7 @@ def parallel_flow_plan(block: nn.Module, cls=None):
     tuple, a norm that carries a forward or forward-pre hook (the fused block reads the norm's parameters and no longer calls it)."""
     cls = cls or type(block)
     norms = {n: m for n, m in block.named_children() if isinstance(m, LayerNormQuant)}
-    if len(norms) not in (1, 2) or any(_norm_is_hooked(m) for m in norms.values()):
+    if len(norms) not in (1, 2) or any(_hooked(m) for m in norms.values()):
         return None
     found = _probe_flow(block, cls, list(norms), _probe_parallel_once, lambda run: run.norm_out[run.attn_norm], _ParallelRun.roles)
     if found is None:
@@ -780,7 +720,7 @@ def parallel_flow_plan(block: nn.Module, cls=None):
     return ParallelPlan(cls, run.attn, run.mlp, run.attn_norm, run.mlp_norm, run3.orders[0], args, kwargs, forwards_extra, withheld, defaults, stateless)
 
 
-class ParallelFusedBlock(nn.Module):
+class ParallelFusedBlock(FusedLayer):
     """A parallel-residual decoder block (GPT-NeoX with use_parallel_residual, Phi) whose three-way sum runs inside the LayerNorm + quantisation kernel of the NEXT
     block (K1pl, add2_layernorm_quantize):
 
@@ -795,19 +735,14 @@ class ParallelFusedBlock(nn.Module):
     the final norm see what they saw.  The norm modules stay the model's, object for object, but are no longer called: only weight / bias / eps are read (which is why
     a block whose norm carries a hook is not converted).  Installed like ResidualFusedBlock — a run-time class deriving from this one and from the original class —
     with the same hand-over discipline and the same fallbacks to the original forward."""
-    _pq_parallel_fused = True
+    _pq_prefix, _pq_parallel_fused = "ParallelFused", True
 
     def forward(self, *args, **kwargs):
         plan = self._pfb_plan
-        bound = plan.signature.bind(self, *args, **kwargs)          # (a TypeError here is the one the original forward would raise)
-        bound.apply_defaults()
-        given = bound.arguments
-        extras = given.get(plan.var_kw_name, {}) if plan.var_kw_name else {}
+        given, extras, out = plan.bind(self, args, kwargs)
+        if given is None:          # (a call the probe did not cover: the original forward ran)
+            return out
         hidden = given[plan.first]
-        if ((self.training and plan.stateless) or not isinstance(hidden, torch.Tensor) or (extras and not plan.var_kw)
-                or any(given[n] is not plan.defaults[n] for n in plan.withheld)):
-            self._rf_inbox.clear()
-            return plan.cls.forward(self, *args, **kwargs)
         handed = self._rf_inbox.take(hidden)
         if handed is not None:
             ha, hm = handed
@@ -817,8 +752,7 @@ class ParallelFusedBlock(nn.Module):
         else:
             n1, n2 = getattr(self, plan.attn_norm), getattr(self, plan.mlp_norm)
             ha, hm = layernorm_quantize2(hidden, n1.weight, n1.bias, n2.weight, n2.bias, n1.eps, n2.eps)
-        value = lambda e: ha if e == _H else given[e[1]] if e[0] == "param" else e[1]          # noqa: E731
-        attn_out = getattr(self, plan.attn)(*(value(e) for e in plan.args), **{k: value(e) for k, e in plan.kwargs.items()}, **extras)[0]
+        attn_out = plan.replay(self, ha, given, extras)[0]
         m = getattr(self, plan.mlp)(hm)
         operand = {"x": hidden, "a": attn_out, "m": m}
         p, q, r = (operand[k] for k in plan.order)
@@ -836,23 +770,6 @@ class ParallelFusedBlock(nn.Module):
         nxt._rf_inbox.put(out, (q1, q2))
         return out
 
-    def __reduce_ex__(self, protocol):          # (the class is made at run time: a copy — deep or pickled — makes it again from the original class)
-        return _rebuild_parallel_block, (self._pfb_plan.cls,), self.__dict__
-
-
-_PFB_CLASSES: dict = {}
-
-
-def _parallel_fused_block_class(cls):
-    if cls not in _PFB_CLASSES:
-        _PFB_CLASSES[cls] = type("ParallelFused" + cls.__name__, (ParallelFusedBlock, cls), {"__doc__": ParallelFusedBlock.__doc__})
-    return _PFB_CLASSES[cls]
-
-
-def _rebuild_parallel_block(cls):
-    fused = _parallel_fused_block_class(cls)
-    return fused.__new__(fused)
-
 
 def fuse_parallel_residual(model: nn.Module) -> int:
     """Opt-in, after fuse_layernorm_layers (which it leaves exactly as it was, as it does fuse_layernorm_residual: an entry of its own): every block of a ModuleList
@@ -861,25 +778,15 @@ def fuse_parallel_residual(model: nn.Module) -> int:
     ModuleList gets the always-called forward hook that drops every pending hand-over when its forward ends.  Returns the number of blocks changed by THIS call (a
     second call finds nothing left to change); parallel_fused_blocks(model) counts them over all calls.  Families whose norms fuse_layernorm_layers does not turn into
     LayerNormQuant (GPT-J, Falcon, Cohere) have nothing to probe: 0, every module object left alone."""
-    n = 0
-    for owner in list(model.modules()):
-        for _, stack in list(owner.named_children()):
-            if not isinstance(stack, nn.ModuleList):
-                continue
-            fresh = []
-            for block in stack:
-                if getattr(type(block), "_pq_parallel_fused", False) or getattr(type(block), "_pq_residual_fused", False):
-                    continue
-                plan = parallel_flow_plan(block)
-                if plan is None:
-                    continue
-                block._pfb_plan = plan
-                block._rf_inbox, block._rf_next = _HandOver(), [None]
-                block.__class__ = _parallel_fused_block_class(plan.cls)
-                fresh.append(block)
-            _link_chain(owner, stack, fresh, ParallelFusedBlock)
-            n += len(fresh)
-    return n
+    def convert(block):
+        if getattr(type(block), "_pq_parallel_fused", False) or getattr(type(block), "_pq_residual_fused", False):
+            return None
+        plan = parallel_flow_plan(block)
+        if plan is None:
+            return None
+        block._pfb_plan = plan
+        return plan.cls
+    return fuse_stacks(model, ParallelFusedBlock, convert)          # (a chain that ends, ends with the two torch adds)
 
 
 def parallel_fused_blocks(model: nn.Module) -> int:

@@ -15,13 +15,13 @@ stay stock torch-ROCm ops.  ``swap_linears(model, fuse_gated_mlp=True)`` must ha
 (``add_rmsnorm_quantize``, kernel K1a: the residual stream is stored once and normalised from registers): see ``ResidualFusedLayer``."""
 from __future__ import annotations
 
-import inspect
-
 import torch
 from torch import nn
 
 from .qlinear import FusedQLinear, GatedMLP, qlinear
 from .qtensor import QTensor, add_rmsnorm_quantize, rmsnorm_quantize
+from .residual_flow import NamedFusedLayer, _forward_extra_params, attention, fuse_stacks, probe_named_flow
+from .residual_flow import _HandOver  # noqa: F401  (the name under which it was introduced here stays importable)
 
 
 class RMSNormQuant(nn.Module):
@@ -100,33 +100,13 @@ def _is_rmsnorm(m) -> bool:
 
 
 # ---------------------------------------------------------------- the residual adds fused into the norms that follow them (opt-in)
-_CHILDREN = ("input_layernorm", "self_attn", "post_attention_layernorm", "mlp")
+_CHILDREN = {"input_layernorm": lambda t: t * 2.0, "self_attn": attention(lambda h: h + 1.0), "post_attention_layernorm": lambda t: t * 0.5 - 3.0,
+             "mlp": lambda t: t * t}
 
 
-class _ProbeRefused(Exception):
-    pass
-
-
-class _ProbeLayer:
-    """Stand-in for `self` in a decoder layer class's own forward: the four children are recording functions, every other attribute is read from the real layer —
-    except another module (a dropout, a third norm): a forward that touches one is not the Llama data flow."""
-
-    def __init__(self, layer: nn.Module, children: dict):
-        self.__dict__["_layer"] = layer
-        self.__dict__.update(children)
-
-    def __getattr__(self, name):
-        v = getattr(self.__dict__["_layer"], name)
-        if isinstance(v, nn.Module):
-            raise _ProbeRefused(f"forward reads the submodule {name!r}")
-        return v
-
-
-def _forward_extra_params(cls) -> tuple:
-    """(names of the positional parameters of cls.forward after hidden_states, whether it takes **kwargs)"""
-    ps = list(inspect.signature(cls.forward).parameters.values())[2:]          # (self, hidden_states, ...)
-    names = tuple(p.name for p in ps if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD))
-    return names, any(p.kind == p.VAR_KEYWORD for p in ps)
+def _llama_flow(x):
+    r1 = x + (x * 2.0 + 1.0)
+    return r1 + (r1 * 0.5 - 3.0) ** 2
 
 
 def residual_flow_is_llama(layer: nn.Module, cls=None) -> bool:
@@ -138,91 +118,10 @@ def residual_flow_is_llama(layer: nn.Module, cls=None) -> bool:
     returned.  Probed, not pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a tiny CPU tensor, and its result
     must EQUAL the formula.  transformers' Llama, Mistral, Qwen2 and Qwen3 layers pass; Granite (residual_multiplier != 1), Gemma-2 and OLMo-2 (post-norms),
     Phi-3 (dropout children), Cohere (parallel block) and any forward that raises on the stand-in do not."""
-    cls = cls or type(layer)
-    try:
-        names, var_kw = _forward_extra_params(cls)
-    except (TypeError, ValueError, AttributeError):
-        return False
-    given = {n: object() for n in names}
-    if var_kw:
-        given["pq_probe_extra"] = object()
-    calls = {c: 0 for c in _CHILDREN}
-    seen = {}
-
-    def norm1(t):
-        calls["input_layernorm"] += 1
-        return t * 2.0
-
-    def attn(*a, **kw):
-        calls["self_attn"] += 1
-        by_name = "hidden_states" in kw
-        h = kw.pop("hidden_states") if by_name else a[0]
-        seen["positional"], seen["kwargs"] = len(a) - (0 if by_name else 1), kw
-        return h + 1.0, None
-
-    def norm2(t):
-        calls["post_attention_layernorm"] += 1
-        return t * 0.5 - 3.0
-
-    def mlp(t):
-        calls["mlp"] += 1
-        return t * t
-
-    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
-    probe = _ProbeLayer(layer, {"input_layernorm": norm1, "self_attn": attn, "post_attention_layernorm": norm2, "mlp": mlp})
-    try:
-        with torch.no_grad():
-            out = cls.forward(probe, x.clone(), **given)
-    except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
-        return False
-    if not isinstance(out, torch.Tensor) or any(n != 1 for n in calls.values()):
-        return False
-    kw = seen["kwargs"]
-    if seen["positional"] != 0 or set(kw) != set(given) or any(kw[k] is not given[k] for k in given):
-        return False
-    r1 = x + (x * 2.0 + 1.0)
-    want = r1 + (r1 * 0.5 - 3.0) ** 2
-    return out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+    return probe_named_flow(layer, cls or type(layer), _CHILDREN, _llama_flow, attn_positional=True)
 
 
-class _HandOver:
-    """The quantised input one layer computed for the next (K1a's second use per layer), keyed by the identity of the tensor it belongs to and that tensor's version
-    counter.  take() empties it whatever the outcome; a copy — deep or pickled — starts empty."""
-    __slots__ = ("_key", "_version", "_q")
-
-    def __init__(self):
-        self.clear()
-
-    @staticmethod
-    def _version_of(t):
-        try:
-            return t._version
-        except Exception:          # noqa: BLE001  (inference tensors track no version counter)
-            return None
-
-    def put(self, key: torch.Tensor, q: QTensor):
-        self._key, self._version, self._q = key, self._version_of(key), q
-
-    def take(self, x):
-        key, version, q = self._key, self._version, self._q
-        self.clear()
-        return q if key is not None and key is x and version == self._version_of(x) else None
-
-    def clear(self):
-        self._key, self._version, self._q = None, None, None
-
-    @property
-    def pending(self) -> bool:
-        return self._key is not None
-
-    def __deepcopy__(self, memo):
-        return _HandOver()
-
-    def __reduce__(self):
-        return (_HandOver, ())
-
-
-class ResidualFusedLayer(nn.Module):
+class ResidualFusedLayer(NamedFusedLayer):
     """A Llama-flow decoder layer whose two residual adds run inside the RMSNorm + quantisation kernels that follow them (K1a, add_rmsnorm_quantize):
 
         h          = the QTensor handed over for this very tensor, else input_layernorm(hidden)
@@ -236,12 +135,11 @@ class ResidualFusedLayer(nn.Module):
     fuse_llama_layers(fuse_residual=True) makes a layer one by giving the layer object a class that derives from this one AND from its original class: the object, its
     four children under their names (state_dict keys), its other attributes, its hooks and every isinstance check on it stay as they were.  The tensor the layer was
     called with is never written; the hand-over is consumed at the next layer's entry and never served for another tensor or a tensor changed in place since."""
+    _pq_prefix = "ResidualFused"
 
     def forward(self, hidden_states, *args, **kwargs):
-        if args:          # positional arguments of the original forward, by its own parameter names
-            if len(args) > len(self._rf_argnames):
-                raise TypeError(f"{type(self).__name__}.forward takes at most {len(self._rf_argnames) + 1} positional arguments")
-            kwargs.update(zip(self._rf_argnames, args))
+        if args:
+            self._fold_positional(args, kwargs)
         h = self._rf_inbox.take(hidden_states)
         if h is None:
             h = self.input_layernorm(hidden_states)
@@ -256,57 +154,19 @@ class ResidualFusedLayer(nn.Module):
         return out
 
 
-_RF_CLASSES: dict = {}
-
-
-def _residual_fused_class(cls):
-    if cls not in _RF_CLASSES:
-        _RF_CLASSES[cls] = type("ResidualFused" + cls.__name__, (ResidualFusedLayer, cls), {"__doc__": ResidualFusedLayer.__doc__})
-    return _RF_CLASSES[cls]
-
-
-def _rf_clear_hook(mod, args, output):
-    for layer in mod._rf_layers:          # (looked up on the module, not captured: a deep copy of the model clears its own layers)
-        layer._rf_inbox.clear()
-
-
-def _link_chain(owner: nn.Module, stack: nn.ModuleList, fresh: list, kind: type) -> None:
-    """After `fresh` layers of `stack` became `kind` (ResidualFusedLayer, or gemma.SandwichFusedLayer): (re)link the chain — a layer hands over to its successor in the
-    stack when that one is of the same kind; anything else ends the chain — and give the owner of the stack its clearing hook, once."""
-    for i, layer in enumerate(stack):
-        if isinstance(layer, kind):
-            nxt = stack[i + 1] if i + 1 < len(stack) else None
-            layer._rf_next = [nxt if isinstance(nxt, kind) else None]          # (a list: the next layer is registered once, in the stack)
-    if fresh:
-        if not hasattr(owner, "_rf_layers"):
-            owner._rf_layers = []
-            owner.register_forward_hook(_rf_clear_hook, always_call=True)          # the owner's forward ended (exceptions included): nothing stays pending
-        owner._rf_layers.extend(fresh)
-
-
 def _fuse_residual(model: nn.Module, only=None) -> int:
     """only (default: every layer): the ids of the layers that may be changed — gemma.fuse_gemma_layers passes the layers it recognised"""
-    n = 0
-    for owner in list(model.modules()):
-        for _, stack in list(owner.named_children()):
-            if not isinstance(stack, nn.ModuleList):
-                continue
-            fresh = []
-            for layer in stack:
-                if isinstance(layer, ResidualFusedLayer) or not all(hasattr(layer, c) for c in _CHILDREN) or (only is not None and id(layer) not in only):
-                    continue
-                if not (isinstance(layer.input_layernorm, RMSNormQuant) and isinstance(layer.post_attention_layernorm, RMSNormQuant)):
-                    continue
-                cls = type(layer)
-                if not residual_flow_is_llama(layer, cls):
-                    continue
-                layer._rf_argnames = _forward_extra_params(cls)[0]
-                layer._rf_inbox, layer._rf_next = _HandOver(), [None]
-                layer.__class__ = _residual_fused_class(cls)
-                fresh.append(layer)
-            _link_chain(owner, stack, fresh, ResidualFusedLayer)          # (a chain that ends, ends with a torch add)
-            n += len(fresh)
-    return n
+    def convert(layer):
+        if isinstance(layer, ResidualFusedLayer) or not all(hasattr(layer, c) for c in _CHILDREN) or (only is not None and id(layer) not in only):
+            return None
+        if not (isinstance(layer.input_layernorm, RMSNormQuant) and isinstance(layer.post_attention_layernorm, RMSNormQuant)):
+            return None
+        cls = type(layer)
+        if not residual_flow_is_llama(layer, cls):
+            return None
+        layer._rf_argnames = _forward_extra_params(cls)[0]
+        return cls
+    return fuse_stacks(model, ResidualFusedLayer, convert)          # (a chain that ends, ends with a torch add)
 
 
 def residual_fused_layers(model: nn.Module) -> int:

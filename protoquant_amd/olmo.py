@@ -23,10 +23,11 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .gemma import _NormStandin, _gemma_formula, _hooked, _llama_formula
-from .llama import _FusedSlice, _HandOver, _ProbeLayer, _SharedFused, _forward_extra_params, _install_qkv_hooks, _link_chain
+from .gemma import _NormStandin, _gemma_formula, _llama_formula
+from .llama import _FusedSlice, _SharedFused, _install_qkv_hooks
 from .qlinear import FusedQLinear, GatedMLP, qlinear
 from .qtensor import olmo_postnorm_add, olmo_postnorm_add_quantize, olmo_rmsnorm, quantize
+from .residual_flow import NamedFusedLayer, _forward_extra_params, _hooked, attention, fuse_stacks, probe_named_flow
 
 
 class OlmoRMSNorm(nn.Module):
@@ -95,7 +96,14 @@ def is_olmo_rmsnorm(m) -> bool:
 
 
 # ---------------------------------------------------------------- is it the post-norm data flow?  (by behaviour)
-_POSTNORM = ("self_attn", "post_attention_layernorm", "mlp", "post_feedforward_layernorm")
+# (the attention is 2 h + 1, not the h + 1 of the flows that have an input norm: it is what tells a missing input norm apart)
+_POSTNORM = {"self_attn": attention(lambda h: h * 2.0 + 1.0), "post_attention_layernorm": lambda t: t * 3.0 - 1.0, "mlp": lambda t: t * t,
+             "post_feedforward_layernorm": lambda t: t * 4.0 + 5.0}
+
+
+def _postnorm_flow(x):
+    r1 = x + ((x * 2.0 + 1.0) * 3.0 - 1.0)
+    return r1 + ((r1 * r1) * 4.0 + 5.0)
 
 
 def residual_flow_is_postnorm(layer: nn.Module, cls=None) -> bool:
@@ -109,48 +117,10 @@ def residual_flow_is_postnorm(layer: nn.Module, cls=None) -> bool:
     gemma.residual_flow_is_sandwich, not pattern-matched: the class's forward runs on a stand-in whose children are cheap exact functions on a tiny CPU tensor, and
     its result must EQUAL the formula.  transformers' Olmo2DecoderLayer and Olmo3DecoderLayer pass; Llama, Gemma-2 and Granite (an input norm: another submodule), a
     layer with a scaled sum, a layer that calls a dropout child and any forward that raises on the stand-in do not."""
-    cls = cls or type(layer)
-    try:
-        names, var_kw = _forward_extra_params(cls)
-    except (TypeError, ValueError, AttributeError):
-        return False
-    given = {n: object() for n in names}
-    if var_kw:
-        given["pq_probe_extra"] = object()
-    calls = {c: 0 for c in _POSTNORM}
-    seen = {}
-
-    def counted(name, f):
-        def run(t):
-            calls[name] += 1
-            return f(t)
-        return run
-
-    def attn(*a, **kw):          # (PostNormFusedLayer calls self_attn(hidden_states=h, **kwargs): that form and no other is accepted)
-        calls["self_attn"] += 1
-        h = kw.pop("hidden_states")
-        seen["positional"], seen["kwargs"] = len(a), kw
-        return h * 2.0 + 1.0, None
-
-    x = torch.arange(-6, 6, dtype=torch.float32).reshape(1, 3, 4)            # small integers: every operation below is exact
-    probe = _ProbeLayer(layer, {"self_attn": attn, "post_attention_layernorm": counted("post_attention_layernorm", lambda t: t * 3.0 - 1.0),
-                                "mlp": counted("mlp", lambda t: t * t), "post_feedforward_layernorm": counted("post_feedforward_layernorm", lambda t: t * 4.0 + 5.0)})
-    try:
-        with torch.no_grad():
-            out = cls.forward(probe, x.clone(), **given)
-    except Exception:          # noqa: BLE001  (whatever the forward raises on the stand-in: refused)
-        return False
-    if not isinstance(out, torch.Tensor) or any(n != 1 for n in calls.values()):
-        return False
-    kw = seen["kwargs"]
-    if seen["positional"] != 0 or set(kw) != set(given) or any(kw[k] is not given[k] for k in given):
-        return False
-    r1 = x + ((x * 2.0 + 1.0) * 3.0 - 1.0)
-    want = r1 + ((r1 * r1) * 4.0 + 5.0)
-    return out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+    return probe_named_flow(layer, cls or type(layer), _POSTNORM, _postnorm_flow)
 
 
-class PostNormFusedLayer(nn.Module):
+class PostNormFusedLayer(NamedFusedLayer):
     """A post-norm decoder layer (OLMo-2, OLMo-3) whose two post-norms and residual adds run inside the quantisation of the next sublayer's input (K1oq,
     olmo_postnorm_add_quantize; K1oa, olmo_postnorm_add, at the end of a chain):
 
@@ -167,13 +137,11 @@ class PostNormFusedLayer(nn.Module):
     AND from its original class: the object, its children under their names, its other attributes, its hooks and every isinstance check on it stay as they were.
     The tensor the layer was called with is never written; the hand-over is consumed at the next layer's entry and never served for another tensor or a tensor
     changed in place since."""
-    _pq_residual_fused = True
+    _pq_prefix, _pq_residual_fused = "PostNormFused", True
 
     def forward(self, hidden_states, *args, **kwargs):
-        if args:          # positional arguments of the original forward, by its own parameter names
-            if len(args) > len(self._rf_argnames):
-                raise TypeError(f"{type(self).__name__}.forward takes at most {len(self._rf_argnames) + 1} positional arguments")
-            kwargs.update(zip(self._rf_argnames, args))
+        if args:
+            self._fold_positional(args, kwargs)
         hq = self._rf_inbox.take(hidden_states)
         if hq is None:
             hq = quantize(hidden_states, axis=-1)
@@ -187,15 +155,6 @@ class PostNormFusedLayer(nn.Module):
         hq2, out = olmo_postnorm_add_quantize(m, pfn.weight, r1, _norm_eps(pfn)[1])
         nxt._rf_inbox.put(out, hq2)
         return out
-
-
-_PF_CLASSES: dict = {}
-
-
-def _postnorm_fused_class(cls):
-    if cls not in _PF_CLASSES:
-        _PF_CLASSES[cls] = type("PostNormFused" + cls.__name__, (PostNormFusedLayer, cls), {"__doc__": PostNormFusedLayer.__doc__})
-    return _PF_CLASSES[cls]
 
 
 def _qkv_state(attn) -> str:
@@ -226,39 +185,33 @@ def fuse_olmo_layers(model: nn.Module, fuse_qkv: bool = True, fuse_residual: boo
 
     Per forward of an L-layer stack the norm and add work is then 1 K1, 2L - 1 K1oq, 1 K1oa and 2L K1on launches, where the swap_linears model runs 4L eager norm
     chains and 2L torch adds on top of its K1 launches.  Out of scope: shard_llama_layers, the final norm, the rotary embedding, FlexOlmo."""
-    n = 0
-    for owner in list(model.modules()):
-        for _, stack in list(owner.named_children()):
-            if not isinstance(stack, nn.ModuleList):
-                continue
-            fresh = []
-            for layer in stack:
-                if {name for name, _ in layer.named_children()} != set(_POSTNORM):
-                    continue
-                attn = layer.self_attn
-                state = _qkv_state(attn)
-                if not state or not residual_flow_is_postnorm(layer, _original_class(layer)):
-                    continue
-                did = False
-                if fuse_qkv and state == "plain":
-                    attn.qkv_fused = _SharedFused(FusedQLinear([attn.q_proj, attn.k_proj, attn.v_proj]))
-                    attn.q_proj, attn.k_proj, attn.v_proj = (_FusedSlice(attn.qkv_fused, i) for i in range(3))
-                    _install_qkv_hooks(attn)
-                    did = True
-                if fuse_residual and not isinstance(layer, PostNormFusedLayer) and _residual_fusable(layer):
-                    for name in ("q_norm", "k_norm"):
-                        old = getattr(attn, name, None)
-                        if is_olmo_rmsnorm(old) and not _hooked(old):
-                            setattr(attn, name, OlmoRMSNorm(old.weight, _norm_eps(old)[1]))
-                    cls = type(layer)
-                    layer._rf_argnames = _forward_extra_params(cls)[0]
-                    layer._rf_inbox, layer._rf_next = _HandOver(), [None]
-                    layer.__class__ = _postnorm_fused_class(cls)
-                    fresh.append(layer)
-                    did = True
-                n += int(did)
-            _link_chain(owner, stack, fresh, PostNormFusedLayer)          # (a chain that ends, ends with K1oa)
-    return n
+    changed = []          # per recognised layer: did this call change it (q / k / v fused, made a PostNormFusedLayer, or both)?
+
+    def convert(layer):
+        if {name for name, _ in layer.named_children()} != set(_POSTNORM):
+            return None
+        attn = layer.self_attn
+        state = _qkv_state(attn)
+        if not state or not residual_flow_is_postnorm(layer, _original_class(layer)):
+            return None
+        cls, did = None, False
+        if fuse_qkv and state == "plain":
+            attn.qkv_fused = _SharedFused(FusedQLinear([attn.q_proj, attn.k_proj, attn.v_proj]))
+            attn.q_proj, attn.k_proj, attn.v_proj = (_FusedSlice(attn.qkv_fused, i) for i in range(3))
+            _install_qkv_hooks(attn)
+            did = True
+        if fuse_residual and not isinstance(layer, PostNormFusedLayer) and _residual_fusable(layer):
+            for name in ("q_norm", "k_norm"):
+                old = getattr(attn, name, None)
+                if is_olmo_rmsnorm(old) and not _hooked(old):
+                    setattr(attn, name, OlmoRMSNorm(old.weight, _norm_eps(old)[1]))
+            cls = type(layer)
+            layer._rf_argnames = _forward_extra_params(cls)[0]
+            did = True
+        changed.append(did)
+        return cls
+    fuse_stacks(model, PostNormFusedLayer, convert)          # (a chain that ends, ends with K1oa)
+    return sum(changed)
 
 
 def _original_class(layer):
