@@ -291,7 +291,9 @@ int32_t pq_gemm_s8s8s32(const int8_t* a, int64_t lda, const int8_t* b, int64_t l
  * output + an exact integer reduction pass, or handed over between the workgroups of a tile inside the GEMM kernel
  * (tickets + per-tile slabs; the call re-initialises the tickets itself): results are bit-identical.  The contents need
  * not be initialised or preserved; one workspace must not serve two calls that may run concurrently.  With
- * workspace == NULL the single-pass kernel runs instead.
+ * workspace == NULL the single-pass kernel runs instead.  A workspace of exactly the queried size is enough, a smaller one is
+ * PQ_ERR_WORKSPACE before anything is launched, and the query is 0 wherever the call would not look at one (a dispatch that has no
+ * split form: M * N < 128^2, at most 64 tokens, a forced variant, a non-positive size): tests/test_gpu_workspace_bounds.py.
  * Liveness of the in-kernel hand-over: the default (ticket) form never waits for a workgroup that may not be running —
  * the workgroups of a tile that finish first store their partial sums and leave, the last one adds them — so it is safe
  * under any placement: several such GEMMs on concurrent streams, CU-masked queues, partitioned devices, a co-running

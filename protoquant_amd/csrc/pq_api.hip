@@ -742,6 +742,9 @@ size_t pq_qlinear_workspace_bytes(int64_t M, int64_t N, int64_t K) {
     {   // (alignment of the operands is unknown here: assume the fast path, as pq_gemm_variant_name does)
         const Variant v = pick_variant(reinterpret_cast<const int8_t*>(16), K, reinterpret_cast<const int8_t*>(16), K, M, N, K);
         if (v == V_RING64X128 || v == V_RING64X64 || v == V_RING128X160) return 0;      // the mid-M tiles and the 128 x 160 tile run single-pass
+        // qlinear_core's `tiled`: every other dispatch (the generic kernel of M * N < 128^2 or of a non-positive size, the weight-streaming kernel, a forced variant)
+        // runs single-pass and never looks at a workspace — the query must not ask for one that the call would not check
+        if (!(v == V_SP256_16 || v == V_SP128_16 || v == V_RING128) || forced_variant() != V_AUTO) return 0;
     }
     if (const int f = fsk_plan(M, N, K)) return pq::fsk_workspace_bytes(M, N, f);
     int tm = 256;
@@ -1063,7 +1066,7 @@ int32_t pq_moe_combine(const void* y, int64_t ldy, int32_t dtype, int64_t M_tota
 
 size_t pq_qlinear_dyn_workspace_bytes(int64_t M, int64_t N, int64_t K) {
     CallScope scope_;
-    if (M < 0 || N < 0 || K < 0) return 0;
+    if (M <= 0 || N <= 0 || K < 0) return 0;      // (M == 0 or N == 0: pq_qlinear_dyn returns before it looks at the workspace; K == 0 still writes the M row scales)
     return align256((size_t)M * (size_t)K) + align256((size_t)M * sizeof(float)) + pq_qlinear_workspace_bytes(M, N, K);
 }
 

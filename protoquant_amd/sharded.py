@@ -511,14 +511,19 @@ class RcclRowReduceScatter:
         m = M // g.world
         code = L.dtype_code(out_dtype)
         need = g._R.lib().pq_reduce_scatter_rows_workspace_bytes(g.world, m, N, code)
-        if need and (self._ws is None or self._ws.numel() < need):
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=partial.device)
+        ws = self._workspace(need, partial.device) if need else None
         out = torch.empty((m, N), dtype=out_dtype, device=partial.device)
         with torch.cuda.device(partial.device):
             g._R.check(g._R.lib().pq_reduce_scatter_rows(g._comm, g.world, partial.data_ptr(), out.data_ptr(), m, N, code,
-                                                         self._ws.data_ptr() if need else None, need, L.stream_ptr(partial)),
+                                                         ws.data_ptr() if need else None, need, L.stream_ptr(partial)),
                        "pq_reduce_scatter_rows")
         return out
+
+    def _workspace(self, need, device):
+        """the f32 sum of a 16-bit output: one buffer, kept and regrown (the one allocator of this class: tests/guarded_workspace.py swaps it)"""
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((need,), dtype=torch.uint8, device=device)
+        return self._ws
 
 
 class RowShardedQLinear(nn.Module):
