@@ -117,10 +117,13 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_rows(row_in_bytes<ADD> x, i
     uint32_t ab = 0;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
+        const int idx = i * TPR + t;
+        // a slot past the row holds a duplicate of the weight's last vector and rs may be Inf or NaN: its h is zero, not 0 * Inf = NaN (which would be the row's
+        // amax).  Zeroed AFTER the arithmetic, as gemma_rmsnorm_quant_rows does (profiles/r22_k1n_dead_slots.txt has the registers and the times of both forms)
         hv[i] = rms_h_vec<DT>(sv[i], wv[i], rs);
+        if (idx >= nvec) hv[i] = v4u{0u, 0u, 0u, 0u};
         ab = vec_amax_bits<DT>(hv[i], ab);
         if constexpr (WRITE_H) {
-            const int idx = i * TPR + t;
             if (active && idx < nvec) store_wt_b128(h_out + row * ldh_bytes + (int64_t)idx * 16, hv[i]);
         }
     }
