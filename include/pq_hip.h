@@ -254,6 +254,21 @@ int32_t pq_gemma_postnorm_add_rmsnorm_quant_rowwise(const void* x, int64_t ld_x,
 int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const void* post_weight, float post_eps, const void* residual, int64_t ld_r, void* sum_out,
                                            int64_t ld_s, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* stream);
 
+/* K1ma — the SCALED residual add of the Granite decoders (r1 = x + attn(norm(x)) * m, out = r1 + mlp(norm(r1)) * m) fused into pq_rmsnorm_quant_rowwise: K1a with one
+ * multiply and one rounding in front of the add.  Per element, with x the sublayer output and residual the residual stream (QSPEC S1, A1):
+ *   p = cast_rne(f32(x) * multiplier)                   S1: one binary32 product, one storage rounding (f32 rows: the binary32 product, rounded on its own); never written
+ *   sum_out = cast_rne(f32(residual) + f32(p))          STORED: the new residual stream (A1) — two roundings, never fma(x, multiplier, residual)
+ *   then N1-N6 and Q1-Q6 on the rows of sum_out AS STORED -> q, scale (and h_out when given).
+ * This is what `residual + x * m` computes in eager torch for a Python number m (rounded once to binary32: it crosses this ABI as a float), so q, scale, sum_out and
+ * h_out are those of pq_add_rmsnorm_quant_rowwise run on p, bit for bit; multiplier == 1 gives K1a's bits.  7 B/elem for 16-bit rows against 13 for the three launches.
+ * K1mo, the add-only form: weight == q == scale == h_out == NULL stops after the add and stores sum_out alone (eps is not read).  A partly-null group is
+ * PQ_ERR_BAD_ARG naming the missing argument.
+ * Arguments, aliasing (sum_out may BE x or residual: same pointer and leading dimension; every other overlap is refused), checks and no-op cases as
+ * pq_add_rmsnorm_quant_rowwise; a NaN or infinite multiplier is PQ_ERR_BAD_ARG naming it.  Row layouts and the PQ_RMS_WAVE_MAX switch as pq_rmsnorm_quant_rowwise (time
+ * only, never bits). */
+int32_t pq_scaled_add_rmsnorm_quant_rows(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, float multiplier, void* sum_out, int64_t ld_s, const void* weight,
+                                         float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* K1gg— K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6

@@ -34,6 +34,7 @@ EXPORTS = (
     "pq_gemma_rmsnorm_quant_rowwise", "pq_add_gemma_rmsnorm_quant_rowwise", "pq_gelu_mul_quant_rowwise",
     "pq_gemma_postnorm_add_rmsnorm_quant_rowwise",
     "pq_olmo_postnorm_add_quant_rowwise",
+    "pq_scaled_add_rmsnorm_quant_rows",
 )
 
 _lib = None
@@ -139,6 +140,8 @@ def lib() -> ctypes.CDLL:
     L.pq_gemma_postnorm_add_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, vp, i64, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_olmo_postnorm_add_quant_rowwise.restype = i32
     L.pq_olmo_postnorm_add_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp]
+    L.pq_scaled_add_rmsnorm_quant_rows.restype = i32
+    L.pq_scaled_add_rmsnorm_quant_rows.argtypes = [vp, i64, vp, i64, ctypes.c_float, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_gelu_mul_quant_rowwise.restype = i32
     L.pq_gelu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
     L.pq_set_option.restype = i32

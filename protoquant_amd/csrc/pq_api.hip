@@ -595,6 +595,32 @@ int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const vo
     return check_launch(fn);
 }
 
+int32_t pq_scaled_add_rmsnorm_quant_rows(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, float multiplier, void* sum_out, int64_t ld_s, const void* weight,
+                                         float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:scaled_add_rmsnorm_quant (K1ma / K1mo)");
+    const char* fn = "pq_scaled_add_rmsnorm_quant_rows";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    if (!(multiplier >= -3.4028234e38f && multiplier <= 3.4028234e38f)) return fail(PQ_ERR_BAD_ARG, "%s: multiplier must be finite (multiplier=%g)", fn, (double)multiplier);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const bool add_only = !weight && !q && !scale && !h_out;          // K1mo: the whole quantisation group is absent (then eps is not read)
+    const char* group = " (weight, q and scale go together: all three and h_out null is the add-only form)";
+    const RowOperand ops[] = {{"x", x, R_IN, "ld_x", ld_x, eb, ""},
+                              {"residual", residual, R_IN, "ld_r", ld_r, eb, ""},
+                              {"sum_out", sum_out, R_INOUT, "ld_s", ld_s, eb, kSumNote},
+                              {"weight", weight, R_IN, nullptr, cols, eb, group},
+                              {"q", q, R_OUT, "ld_q", ld_q, 1, group},
+                              {"scale", scale, R_OUT, nullptr, rows, 4, group},
+                              {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    const float no_eps = 0.0f;
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, add_only ? &no_eps : &eps, ops, add_only ? 3 : 7, &empty); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) {
+        pq::scaled_add_rmsnorm_quant_dispatch<dt>(x, ld_x, residual, ld_r, multiplier, sum_out, ld_s, weight, eps, rows, cols, q, ld_q, scale, h_out, ld_h, st);
+    });
+    return check_launch(fn);
+}
+
 int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q,
                                   float* scale, void* h_out, int64_t ld_h, void* stream) {
     Range range_("pq:gelu_mul_quant (K1gg)");

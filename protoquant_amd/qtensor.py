@@ -290,6 +290,80 @@ def add_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: torch.
     return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
 
 
+def _residual_multiplier(what: str, multiplier) -> float:
+    """`multiplier` as the C-ABI takes it: a finite Python int or float (a tensor would be a device value the kernel cannot take as an argument; bool is no number here)"""
+    if isinstance(multiplier, bool) or not isinstance(multiplier, (int, float)):
+        raise TypeError(f"{what}: multiplier must be a Python int or float, got {type(multiplier).__name__}")
+    m = float(multiplier)
+    if m != m or m in (float("inf"), float("-inf")):
+        raise ValueError(f"{what}: multiplier must be finite, got {multiplier!r}")
+    return m
+
+
+def _scaled_operands(what: str, x, residual, out):
+    """the shape / dtype / device checks of K1a on x, residual and the optional destination of the sum"""
+    L.require_gpu(x, f"{what}(x)")
+    L.require_gpu(residual, f"{what}(residual)")
+    if x.dim() < 1 or x.shape != residual.shape or x.dtype != residual.dtype or x.device != residual.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} {x.device} and residual {tuple(residual.shape)} {residual.dtype} {residual.device} must match")
+    if out is not None:
+        L.require_gpu(out, f"{what}(out)")
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"{what}: out {tuple(out.shape)} {out.dtype} must have x's shape {tuple(x.shape)} and dtype {x.dtype}")
+
+
+def scaled_add_rmsnorm_quantize(x: torch.Tensor, residual: torch.Tensor, multiplier, weight: torch.Tensor, eps: float = 1e-6, out: torch.Tensor | None = None,
+                                return_h: bool = False):
+    """summed = residual + x * multiplier, then rmsnorm_quantize(summed, weight, eps) — in ONE kernel (K1ma): the scaled residual add of the Granite decoders taken into the
+    norm + quantisation that follows it.  Returns (QTensor, summed) or (QTensor, summed, h) with return_h=True; every one of them holds the bits of
+    add_rmsnorm_quantize(x * multiplier, residual, weight, eps, return_h=True) with the product computed by torch (QSPEC S1: one binary32 product, rounded to the storage
+    dtype BEFORE the add — two roundings, never a fused multiply-add; then A1, N1-N6, Q1-Q6).  `multiplier` is a finite Python int or float (a tensor is a TypeError); it
+    is rounded once to binary32, as torch rounds a Python scalar.  x, residual, weight, `out` and the aliasing rule as add_rmsnorm_quantize.  There is no CPU path."""
+    what = "scaled_add_rmsnorm_quantize"
+    m = _residual_multiplier(what, multiplier)
+    _scaled_operands(what, x, residual, out)
+    L.require_gpu(weight, f"{what}(weight)")
+    if weight.dim() != 1 or weight.shape[0] != x.shape[-1] or weight.dtype != x.dtype or weight.device != x.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} needs a weight of shape ({x.shape[-1]},) and the same dtype/device, "
+                         f"got {tuple(weight.shape)} {weight.dtype}")
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, what)
+    if rows == 0 or cols == 0:          # nothing to add: the empty sum through K1n (scales of empty rows are 1, QSPEC Q3)
+        res = rmsnorm_quantize(summed, weight, eps, return_h)
+        return (res[0], summed, res[1]) if return_h else (res, summed)
+    w = weight.contiguous()
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    h = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if return_h else None
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_scaled_add_rmsnorm_quant_rows(x2.data_ptr(), L.ld(x2), r2.data_ptr(), L.ld(r2), m, s2.data_ptr(), L.ld(s2), w.data_ptr(), float(eps), code, rows,
+                                                         cols, q.data_ptr(), cols, scale.data_ptr(), h.data_ptr() if return_h else None, cols, L.stream_ptr(x)), what)
+    qt = QTensor(q.reshape(x.shape), scale, 1, x.dtype, x.shape)
+    return (qt, summed, h.reshape(x.shape)) if return_h else (qt, summed)
+
+
+def scaled_add(x: torch.Tensor, residual: torch.Tensor, multiplier, out: torch.Tensor | None = None) -> torch.Tensor:
+    """residual + x * multiplier in ONE kernel (K1mo, the add-only form of K1ma: the end of a chain of Granite layers) — the bits of the torch expression (QSPEC S1, A1:
+    the product is rounded to the storage dtype before the add).  Operands, `multiplier`, `out` and the aliasing rule as scaled_add_rmsnorm_quantize.  Returns the sum."""
+    what = "scaled_add"
+    m = _residual_multiplier(what, multiplier)
+    _scaled_operands(what, x, residual, out)
+    code = L.dtype_code(x.dtype)
+    x2, r2 = _rows_view(x), _rows_view(residual)
+    rows, cols = x2.shape
+    summed = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    s2 = _rows_view_of_out(summed, rows, cols, what)
+    if rows == 0 or cols == 0:
+        return summed
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_scaled_add_rmsnorm_quant_rows(x2.data_ptr(), L.ld(x2), r2.data_ptr(), L.ld(r2), m, s2.data_ptr(), L.ld(s2), None, 0.0, code, rows, cols, None, cols,
+                                                         None, None, cols, L.stream_ptr(x)), what)
+    return summed
+
+
 def layernorm_quantize(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, eps: float = 1e-5, return_h: bool = False):
     """quantize(F.layer_norm(x, (C,), weight, bias, eps), axis=-1) in ONE pass (kernel K1l: K1 fused into LayerNorm): the normalised activation feeding c_attn /
     q, k, v / c_fc is reduced, normalised and encoded in registers.  `weight` is required (a LayerNorm without affine parameters is refused); `bias` may be None.
