@@ -13,19 +13,9 @@ namespace pq {
 template <int DT>
 void add_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, float eps, int64_t rows,
                                 int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st) {
-    const int64_t kb = Elem<DT>::kBytes;
-    rownorm_dispatch<DT>(
-        {{x, ldx}, {res, ldr}, {sum_out, lds}, {wgt, 0}}, rows, cols, q, ldq, h_out, ldh,
-        [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
-            rmsnorm_quant_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(write_h)::value, true><<<grid, dim3(256), 0, st>>>(
-                reinterpret_cast<const uint8_t*>(x), ldx * kb, reinterpret_cast<const uint8_t*>(res), ldr * kb, reinterpret_cast<uint8_t*>(sum_out), lds * kb,
-                reinterpret_cast<const uint8_t*>(wgt), eps, (int)cols, nvec, rows, q, ldq, scale, reinterpret_cast<uint8_t*>(h_out), ldh * kb);
-        },
-        [&](dim3 grid) { rmsnorm_quant_generic<DT, true><<<grid, dim3(256), 0, st>>>(x, ldx, res, ldr, sum_out, lds, wgt, eps, cols, q, ldq, scale, h_out, ldh); });
+    rmsnorm_rows_dispatch<DT, true, LlamaGain>(x, ldx, res, ldr, sum_out, lds, wgt, eps, rows, cols, q, ldq, scale, h_out, ldh, st);
 }
 
-template void add_rmsnorm_quant_dispatch<PQ_BF16>(const void*, int64_t, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void add_rmsnorm_quant_dispatch<PQ_FP16>(const void*, int64_t, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void add_rmsnorm_quant_dispatch<PQ_F32>(const void*, int64_t, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+PQ_INSTANTIATE_DTYPES(add_rmsnorm_quant_dispatch)
 
 }  // namespace pq

@@ -5,51 +5,19 @@
 //   K1pang only:  GemmaRMSNorm(s; weight, eps) on the rows of s AS STORED -> int8 codes + row scales (+ the normalised activation when asked for)
 // One kernel where a Gemma-2 decoder layer ran the eager GemmaRMSNorm chain, a torch add and K1ng.  Algorithmic traffic for 16-bit rows: 7 B/elem (x and the
 // residual read, s and the codes written; the two weight rows are cache-resident) — K1ang's; K1pa 6 B/elem.
-// The row template is this file's own (gemma_rownorm_kernels.h: a parameter added to a shipped template changes the register allocation of the shipped kernels);
-// the arithmetic (gemma_h_vec, add_vec), the pinned order of both sums of squares (row_sum), rs (rms_rs), the row layouts (rownorm_dispatch) and the second half
-// of K1 (reduce_and_encode) are the family's.
+// The arithmetic (GemmaGain, add_vec), the lane's sum of squares and the row sum in their pinned order (lane_sumsq, rms_row_sum), rs (rms_rs), the row layouts
+// (rownorm_dispatch) and the second half of K1 (reduce_and_encode) are the family's (rownorm_kernels.h).  The row template stays this file's own: its second half is
+// K1ang's and its first half OLMo's with another gain, but with either as a shared __forceinline__ function most of the 87 kernels compile to other instructions,
+// and they were not timed against their predecessors ("The RMS row kernels on one template").
 // Aliasing: sum_out may be exactly x or exactly residual.  A row belongs to one wave or workgroup; rs_p needs the WHOLE of x, so every element of x is read (into
 // registers; generic kernel: in a pass of its own, closed by a block barrier) before any element of s is written, and x is never read again once s is stored.
 // Registers: x and the residual are in flight together, post_weight with them or once the lane's pass over x is done (3 vectors per slot); p takes x's place and
 // post_weight's die, s takes p's place and the residual's die; `weight` is asked for only then (pin_before_loads), before the stores of s, and h makes it 3 per
 // slot again — K1ang's peak (s, weight, h).
-#include "gemma_rownorm_kernels.h"
+#include "rownorm_kernels.h"
 #include "pq_launch.h"
 
 namespace pq {
-
-// this lane's share of the sum of squares of a row held in registers (NG2: vectors in increasing v, elements in order; slots past the row are zeroed first), one
-// accumulator per 64-lane group of the specification (rownorm_kernels.h, "Row layouts"); row_sum adds them in the pinned order (NG3)
-template <int DT, int VPT, int TPR>
-__device__ __forceinline__ void postnorm_lane_sumsq(v4u (&sv)[VPT], int t, int nvec, float (&acc)[TPR == 64 ? 4 : 1]) {
-    constexpr int EPV = 16 / Elem<DT>::kBytes;
-    constexpr int NACC = TPR == 64 ? 4 : 1;
-#pragma unroll
-    for (int gi = 0; gi < NACC; ++gi) acc[gi] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        if (i * TPR + t >= nvec) sv[i] = v4u{0u, 0u, 0u, 0u};      // past the row: fma(0, 0, acc) = acc
-        float f[EPV];
-        Unpack<DT, EPV>::run(sv[i], f);
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) acc[i & (NACC - 1)] = __builtin_fmaf(f[j], f[j], acc[i & (NACC - 1)]);
-    }
-}
-
-// the row's sum from the lanes' accumulators (NG3).  One wave per row: row_sum<64>'s butterfly, written out as gemma_rmsnorm_quant_rows has it
-template <int TPR>
-__device__ __forceinline__ float postnorm_row_sum(float (&acc)[TPR == 64 ? 4 : 1]) {
-    if constexpr (TPR == 64) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) acc[gi] = acc[gi] + __shfl_xor(acc[gi], off, 64);
-        }
-        return ((acc[0] + acc[1]) + acc[2]) + acc[3];
-    } else {
-        return rms_block_sum(acc[0]);
-    }
-}
 
 // K1pang (QUANT) / K1pa (!QUANT; wgt, q, scale and h_out are null and never touched)
 template <int DT, int VPT, int TPR, bool WRITE_H, bool QUANT>
@@ -78,15 +46,15 @@ __global__ __launch_bounds__(256) void gemma_postnorm_add_rows(const uint8_t* x,
             rv[i] = *reinterpret_cast<const v4u*>(rr + off);
             if constexpr (PW_FIRST) pv[i] = *reinterpret_cast<const v4u*>(pwgt + off);
         }
-        postnorm_lane_sumsq<DT, VPT, TPR>(sv, t, nvec, acc);                                           // NG2 on x
+        lane_sumsq<DT, VPT, TPR>(sv, t, nvec, acc);                                           // NG2 on x
         if constexpr (!PW_FIRST) {
             pin_before_loads(sv);
 #pragma unroll
             for (int i = 0; i < VPT; ++i) pv[i] = *reinterpret_cast<const v4u*>(pwgt + clamped_vec_off(i * TPR + t, nvec));
         }
-        const float rs_p = rms_rs(postnorm_row_sum<TPR>(acc), cols, post_eps);                                  // NG3, NG4
+        const float rs_p = rms_rs(rms_row_sum<TPR>(acc), cols, post_eps);                                  // NG3, NG4
 #pragma unroll
-        for (int i = 0; i < VPT; ++i) sv[i] = gemma_h_vec<DT>(sv[i], pv[i], rs_p);                     // PN1: p, rounded to the storage dtype, takes the place of x
+        for (int i = 0; i < VPT; ++i) sv[i] = GemmaGain::h_vec<DT>(sv[i], pv[i], rs_p);                     // PN1: p, rounded to the storage dtype, takes the place of x
 #pragma unroll
         for (int i = 0; i < VPT; ++i) sv[i] = add_vec<DT>(sv[i], rv[i]);                               // A1: the sum takes the place of p
         pin_before_loads(sv);
@@ -107,14 +75,14 @@ __global__ __launch_bounds__(256) void gemma_postnorm_add_rows(const uint8_t* x,
         if constexpr (TPR == 256) __syncthreads();                 // row_sum<256>'s four partial sums are one array: everyone has read the first sum
         // NG2-NG4 on s AS STORED (a slot past the row held p = (0 * rs_p) * g + a duplicate of the residual: zeroed in there)
         float acc[TPR == 64 ? 4 : 1];
-        postnorm_lane_sumsq<DT, VPT, TPR>(sv, t, nvec, acc);
-        const float rs = rms_rs(postnorm_row_sum<TPR>(acc), cols, eps);
+        lane_sumsq<DT, VPT, TPR>(sv, t, nvec, acc);
+        const float rs = rms_rs(rms_row_sum<TPR>(acc), cols, eps);
         v4u hv[VPT];
         uint32_t ab = 0;
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             const int idx = i * TPR + t;
-            hv[i] = gemma_h_vec<DT>(sv[i], wv[i], rs);             // zeroed AFTER the arithmetic, as gemma_rmsnorm_quant_rows does
+            hv[i] = GemmaGain::h_vec<DT>(sv[i], wv[i], rs);             // zeroed AFTER the arithmetic, as rmsnorm_quant_rows does
             if (idx >= nvec) hv[i] = v4u{0u, 0u, 0u, 0u};
             ab = vec_amax_bits<DT>(hv[i], ab);
             if constexpr (WRITE_H) {
@@ -146,7 +114,7 @@ __global__ __launch_bounds__(256) void gemma_postnorm_add_generic(const void* x,
     const float rs_p = rms_rs(rms_block_sum(acc), (int)cols, post_eps);
     acc = 0.0f;
     walk_row<DT, true>(cols, [&](int64_t c) {
-        const S p = Elem<DT>::from_f32(gemma_h(Elem<DT>::to_f32(xr[c]), Elem<DT>::to_f32(pr[c]), rs_p));      // PN1
+        const S p = Elem<DT>::from_f32(GemmaGain::h<DT>(Elem<DT>::to_f32(xr[c]), Elem<DT>::to_f32(pr[c]), rs_p));      // PN1
         const S s = add_elem<DT>(rr[c], p);                                                                   // A1
         sr[c] = s;
         if constexpr (QUANT) {
@@ -160,7 +128,7 @@ __global__ __launch_bounds__(256) void gemma_postnorm_add_generic(const void* x,
         __syncthreads();                    // rms_block_sum's partial sums are one array: everyone has read the first sum
         const float rs = rms_rs(rms_block_sum(acc), (int)cols, eps);
         generic_amax_and_encode<DT, true>(
-            row, cols, [&](int64_t c) -> S { return Elem<DT>::from_f32(gemma_h(Elem<DT>::to_f32(in[c]), Elem<DT>::to_f32(wr[c]), rs)); }, q, ldq, scale, h_out, ldh);
+            row, cols, [&](int64_t c) -> S { return Elem<DT>::from_f32(GemmaGain::h<DT>(Elem<DT>::to_f32(in[c]), Elem<DT>::to_f32(wr[c]), rs)); }, q, ldq, scale, h_out, ldh);
     }
 }
 
@@ -170,31 +138,19 @@ void gemma_postnorm_add_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const
                                                const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh,
                                                hipStream_t st) {
     const int64_t kb = Elem<DT>::kBytes;
-    const bool quant = wgt != nullptr;
-    const auto b = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
-    rownorm_dispatch<DT>(
-        {{x, ldx}, {res, ldr}, {sum_out, lds}, {pwgt, 0}, {wgt, 0}}, rows, cols, q, quant ? ldq : 0, h_out, ldh,
-        [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
-            constexpr int VPT = decltype(vpt)::value, TPR = decltype(tpr)::value;
-            constexpr bool WRITE_H = decltype(write_h)::value;
-            if (quant) {
-                gemma_postnorm_add_rows<DT, VPT, TPR, WRITE_H, true><<<grid, dim3(256), 0, st>>>(b(x), ldx * kb, b(pwgt), post_eps, b(res), ldr * kb,
-                                                                                                 reinterpret_cast<uint8_t*>(sum_out), lds * kb, b(wgt), eps, (int)cols, nvec, rows,
-                                                                                                 q, ldq, scale, reinterpret_cast<uint8_t*>(h_out), ldh * kb);
-            } else if constexpr (!WRITE_H) {
-                gemma_postnorm_add_rows<DT, VPT, TPR, false, false><<<grid, dim3(256), 0, st>>>(b(x), ldx * kb, b(pwgt), post_eps, b(res), ldr * kb,
-                                                                                                reinterpret_cast<uint8_t*>(sum_out), lds * kb, nullptr, 0.0f, (int)cols, nvec, rows,
-                                                                                                nullptr, 0, nullptr, nullptr, 0);
-            }
+    rownorm_dispatch_quant_or_sum<DT>(
+        {{x, ldx}, {res, ldr}, {sum_out, lds}, {pwgt, 0}, {wgt, 0}}, rows, cols, wgt != nullptr, q, ldq, h_out, ldh,
+        [&](auto vpt, auto tpr, auto write_h, auto quant, dim3 grid, int nvec) {
+            gemma_postnorm_add_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(write_h)::value, decltype(quant)::value><<<grid, dim3(256), 0, st>>>(
+                row_bytes(x), ldx * kb, row_bytes(pwgt), post_eps, row_bytes(res), ldr * kb, row_bytes(sum_out), lds * kb, row_bytes(wgt), eps, (int)cols, nvec, rows, q,
+                ldq, scale, row_bytes(h_out), ldh * kb);
         },
-        [&](dim3 grid) {
-            if (quant) gemma_postnorm_add_generic<DT, true><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, wgt, eps, cols, q, ldq, scale, h_out, ldh);
-            else gemma_postnorm_add_generic<DT, false><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, nullptr, 0.0f, cols, nullptr, 0, nullptr, nullptr, 0);
+        [&](auto quant, dim3 grid) {
+            gemma_postnorm_add_generic<DT, decltype(quant)::value><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, wgt, eps, cols, q, ldq, scale, h_out,
+                                                                                               ldh);
         });
 }
 
-template void gemma_postnorm_add_rmsnorm_quant_dispatch<PQ_BF16>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void gemma_postnorm_add_rmsnorm_quant_dispatch<PQ_FP16>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void gemma_postnorm_add_rmsnorm_quant_dispatch<PQ_F32>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+PQ_INSTANTIATE_DTYPES(gemma_postnorm_add_rmsnorm_quant_dispatch)
 
 }  // namespace pq

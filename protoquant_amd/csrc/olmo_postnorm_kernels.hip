@@ -5,9 +5,11 @@
 //   K1oa:  s = residual + p  STORED, nothing else (q == scale == nullptr: the end of a chain)
 //   K1on:  p STORED to sum_out, nothing else (residual == nullptr as well: the norm alone, q_norm / k_norm)
 // Algorithmic traffic for 16-bit rows: K1oq 7 B/elem (x and the residual read, s and the codes written; the weight row is cache-resident), K1oa 6, K1on 4.
-// The row template is this file's own (gemma_rownorm_kernels.h: a parameter added to a shipped template changes the register allocation of the shipped kernels); the
-// pinned order of the sum of squares (row_sum), rs (rms_rs), A1 (add_vec), the row layouts (rownorm_dispatch) and the second half of K1 (reduce_and_encode) are the
-// family's.  There is ONE sum of squares and ONE weight row: what is quantised is the stored sum itself, not a second norm of it.
+// The gain (OlmoGain: NO5), the pinned order of the sum of squares (row_sum), rs (rms_rs), A1 (add_vec), the row layouts (rownorm_dispatch) and the second half of K1
+// (reduce_and_encode) are the family's (rownorm_kernels.h).  There is ONE sum of squares and ONE weight row: what is quantised is the stored sum itself, not a second
+// norm of it.  The row template stays this file's own, with its steps written out: its first half is K1pang's with another gain and an optional add, but as one
+// __forceinline__ function for both, 72 of the 90 kernels here and 67 of K1pang's 87 compile to other instructions, and these kernels were not timed against their
+// predecessors ("The RMS row kernels on one template").
 // Aliasing: sum_out may be exactly x or exactly residual.  A row belongs to one wave or workgroup; rs needs the WHOLE of x, so every element of x is read (into
 // registers; generic kernel: in a pass of its own, closed by a block barrier) before any element of s is written, and x is never read again once s is stored.
 // Registers: x, the residual and post_weight are in flight together at the peak (3 vectors per slot; K1on 2); p takes x's place and post_weight's die, s takes p's
@@ -16,29 +18,6 @@
 #include "pq_launch.h"
 
 namespace pq {
-
-// NO5 for one element: h = (x * rs) * w, every operation rounded in binary32 (the build has no contraction); the caller rounds to the storage dtype
-__device__ __forceinline__ float olmo_h(float x, float w, float rs) { return (x * rs) * w; }
-
-// one 16-byte vector of x and of the weight -> one 16-byte vector of h (NO5), two elements per instruction
-template <int DT>
-__device__ __forceinline__ v4u olmo_h_vec(const v4u& xv, const v4u& wv, float rs) {
-    v4u out;
-    if constexpr (DT == PQ_F32) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t xb = xv[j], wb = wv[j];      // copies first (hipcc quirk with vector-element lvalues)
-            out[j] = __builtin_bit_cast(uint32_t, olmo_h(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, wb), rs));
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t xw = xv[j], ww = wv[j];
-            out[j] = Pair<DT>::pack((Pair<DT>::unpack(xw) * splat(rs)) * Pair<DT>::unpack(ww));
-        }
-    }
-    return out;
-}
 
 // K1oq (ADD, QUANT) / K1oa (ADD; q and scale are null and never touched) / K1on (neither; res is null as well)
 template <int DT, int VPT, int TPR, bool ADD, bool QUANT>
@@ -84,7 +63,7 @@ __global__ __launch_bounds__(256) void olmo_postnorm_rows(const uint8_t* x, int6
         }
         const float rs = rms_rs(row_sum<TPR>(acc), cols, post_eps);                                    // NO3, NO4
 #pragma unroll
-        for (int i = 0; i < VPT; ++i) sv[i] = olmo_h_vec<DT>(sv[i], pv[i], rs);                        // NO5 / PO1: p, rounded to the storage dtype, takes the place of x
+        for (int i = 0; i < VPT; ++i) sv[i] = OlmoGain::h_vec<DT>(sv[i], pv[i], rs);                        // NO5 / PO1: p, rounded to the storage dtype, takes the place of x
         if constexpr (ADD) {
 #pragma unroll
             for (int i = 0; i < VPT; ++i) sv[i] = add_vec<DT>(sv[i], rv[i]);                           // A1: the sum takes the place of p
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(256) void olmo_postnorm_generic(const void* x, int6
     });
     const float rs = rms_rs(rms_block_sum(acc), (int)cols, post_eps);
     walk_row<DT, true>(cols, [&](int64_t c) {
-        const S p = Elem<DT>::from_f32(olmo_h(Elem<DT>::to_f32(xr[c]), Elem<DT>::to_f32(pr[c]), rs));      // NO5 / PO1
+        const S p = Elem<DT>::from_f32(OlmoGain::h<DT>(Elem<DT>::to_f32(xr[c]), Elem<DT>::to_f32(pr[c]), rs));      // NO5 / PO1
         if constexpr (ADD) sr[c] = add_elem<DT>(rr[c], p);                                                 // A1
         else sr[c] = p;
     });
@@ -143,27 +122,29 @@ void olmo_postnorm_add_quant_dispatch(const void* x, int64_t ldx, const void* pw
                                       int64_t cols, int8_t* q, int64_t ldq, float* scale, hipStream_t st) {
     const int64_t kb = Elem<DT>::kBytes;
     const bool add = res != nullptr, quant = q != nullptr;
-    const auto b = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
-    uint8_t* so = reinterpret_cast<uint8_t*>(sum_out);
+    // the form as two integral constants (ADD, QUANT), handed to f
+    const auto with_form = [&](auto f) {
+        if (quant) f(std::true_type{}, std::true_type{});
+        else if (add) f(std::true_type{}, std::false_type{});
+        else f(std::false_type{}, std::false_type{});
+    };
     rownorm_dispatch<DT>(
         {{x, ldx}, {res, add ? ldr : 0}, {sum_out, lds}, {pwgt, 0}}, rows, cols, q, quant ? ldq : 0, nullptr, 0,
         [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
-            constexpr int VPT = decltype(vpt)::value, TPR = decltype(tpr)::value;
             if constexpr (!decltype(write_h)::value) {          // (there is no h_out: s is what is quantised, and it is stored)
-                if (quant) olmo_postnorm_rows<DT, VPT, TPR, true, true><<<grid, dim3(256), 0, st>>>(b(x), ldx * kb, b(pwgt), post_eps, b(res), ldr * kb, so, lds * kb, (int)cols, nvec, rows, q, ldq, scale);
-                else if (add) olmo_postnorm_rows<DT, VPT, TPR, true, false><<<grid, dim3(256), 0, st>>>(b(x), ldx * kb, b(pwgt), post_eps, b(res), ldr * kb, so, lds * kb, (int)cols, nvec, rows, nullptr, 0, nullptr);
-                else olmo_postnorm_rows<DT, VPT, TPR, false, false><<<grid, dim3(256), 0, st>>>(b(x), ldx * kb, b(pwgt), post_eps, nullptr, 0, so, lds * kb, (int)cols, nvec, rows, nullptr, 0, nullptr);
+                with_form([&](auto a, auto qn) {
+                    olmo_postnorm_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(a)::value, decltype(qn)::value><<<grid, dim3(256), 0, st>>>(
+                        row_bytes(x), ldx * kb, row_bytes(pwgt), post_eps, row_bytes(res), ldr * kb, row_bytes(sum_out), lds * kb, (int)cols, nvec, rows, q, ldq, scale);
+                });
             }
         },
         [&](dim3 grid) {
-            if (quant) olmo_postnorm_generic<DT, true, true><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, cols, q, ldq, scale);
-            else if (add) olmo_postnorm_generic<DT, true, false><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, cols, nullptr, 0, nullptr);
-            else olmo_postnorm_generic<DT, false, false><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, nullptr, 0, sum_out, lds, cols, nullptr, 0, nullptr);
+            with_form([&](auto a, auto qn) {
+                olmo_postnorm_generic<DT, decltype(a)::value, decltype(qn)::value><<<grid, dim3(256), 0, st>>>(x, ldx, pwgt, post_eps, res, ldr, sum_out, lds, cols, q, ldq, scale);
+            });
         });
 }
 
-template void olmo_postnorm_add_quant_dispatch<PQ_BF16>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, hipStream_t);
-template void olmo_postnorm_add_quant_dispatch<PQ_FP16>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, hipStream_t);
-template void olmo_postnorm_add_quant_dispatch<PQ_F32>(const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int64_t, int64_t, int8_t*, int64_t, float*, hipStream_t);
+PQ_INSTANTIATE_DTYPES(olmo_postnorm_add_quant_dispatch)
 
 }  // namespace pq

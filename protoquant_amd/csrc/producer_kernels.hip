@@ -75,20 +75,10 @@ void silu_mul_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t 
 template <int DT>
 void rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* wgt, float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
                             void* h_out, int64_t ldh, hipStream_t st) {
-    const int64_t kb = Elem<DT>::kBytes;
-    rownorm_dispatch<DT>(
-        {{x, ldx}, {wgt, 0}}, rows, cols, q, ldq, h_out, ldh,
-        [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
-            rmsnorm_quant_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(write_h)::value, false><<<grid, dim3(256), 0, st>>>(
-                reinterpret_cast<const uint8_t*>(x), ldx * kb, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(wgt), eps, (int)cols, nvec, rows, q, ldq,
-                scale, reinterpret_cast<uint8_t*>(h_out), ldh * kb);
-        },
-        [&](dim3 grid) { rmsnorm_quant_generic<DT, false><<<grid, dim3(256), 0, st>>>(x, ldx, nullptr, 0, nullptr, 0, wgt, eps, cols, q, ldq, scale, h_out, ldh); });
+    rmsnorm_rows_dispatch<DT, false, LlamaGain>(x, ldx, nullptr, 0, nullptr, 0, wgt, eps, rows, cols, q, ldq, scale, h_out, ldh, st);
 }
 
-template void rmsnorm_quant_dispatch<PQ_BF16>(const void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void rmsnorm_quant_dispatch<PQ_FP16>(const void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
-template void rmsnorm_quant_dispatch<PQ_F32>(const void*, int64_t, const void*, float, int64_t, int64_t, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+PQ_INSTANTIATE_DTYPES(rmsnorm_quant_dispatch)
 
 #define PQ_SPLIT_INST(DT) \
     template void silu_mul_split_dispatch<DT, 1, false>(const void*, int64_t, const void*, int64_t, int64_t, int64_t, uint32_t*, int8_t*, int64_t, float*, hipStream_t); \

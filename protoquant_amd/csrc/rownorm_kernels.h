@@ -1,9 +1,11 @@
 // rownorm_kernels.h — the kernels and the dispatch of the norm-into-quantisation family: a normalisation (optionally behind a residual add) fused into the
 // per-token int8 quantisation, without the normalised activation ever going to HBM.
-//   rmsnorm_quant_rows<.., ADD = false>     K1n   RMSNorm(x; weight)           -> codes + row scales   (instantiated in producer_kernels.hip)
-//   rmsnorm_quant_rows<.., ADD = true>      K1a   s = x + residual (stored), then K1n on s             (addnorm_kernels.hip)
-//   layernorm_quant_rows<.., ADD = false>   K1l   LayerNorm(x; weight, bias)   -> codes + row scales   (layernorm_kernels.hip)
-//   layernorm_quant_rows<.., ADD = true>    K1al  s = x + residual (stored), then K1l on s             (addlayernorm_kernels.hip)
+//   rmsnorm_quant_rows<.., ADD = false, LlamaGain>        K1n    RMSNorm(x; weight)          -> codes + row scales   (instantiated in producer_kernels.hip)
+//   rmsnorm_quant_rows<.., ADD = true, LlamaGain>         K1a    s = x + residual (stored), then K1n on s            (addnorm_kernels.hip)
+//   rmsnorm_quant_rows<.., ADD, GemmaGain>                K1ng / K1ang   the same with GemmaRMSNorm's gain 1 + w     (gemma_norm_kernels.hip, add_gemma_norm_kernels.hip)
+//   rmsnorm_quant_rows<.., true, LlamaGain, QUANT, float> K1ma / K1mo    s = residual + cast(x * mult) (stored), then K1n on s / nothing more   (scaled_addnorm_kernels.hip)
+//   layernorm_quant_rows<.., ADD = false>                 K1l    LayerNorm(x; weight, bias)  -> codes + row scales   (layernorm_kernels.hip)
+//   layernorm_quant_rows<.., ADD = true>                  K1al   s = x + residual (stored), then K1l on s            (addlayernorm_kernels.hip)
 // and one generic kernel per norm for ragged widths and unaligned operands.  The kernels are templates: a translation unit instantiates those that its
 // *_quant_dispatch launches and no others, so each member of the family keeps an object file, and a register allocation, of its own.
 // Row layouts (QSPEC N1-N3 / L2-L3 pin the ORDER of the row sums; the layout changes time only, never bits):
@@ -19,7 +21,9 @@
 // end load a clamped duplicate of the row's last vector, which another thread (or an in-place h_out) may be overwriting: they are zeroed before any use.
 // Register allocation.  The bodies are the __global__ templates themselves (a wrapper around an inlined body costs up to 26 VGPRs), their helpers are
 // __forceinline__ functions and not lambdas, and the row's arrays are declared in the order x / sum, residual, weight, bias: each of these decides whether hipcc
-// gives a kernel the instruction stream it had as a kernel of its own (profiles/r17_rownorm_kernels.txt compares all 228 with their predecessors).
+// gives a kernel the instruction stream it had as a kernel of its own (profiles/r17_rownorm_kernels.txt compares all 228 with their predecessors).  A template
+// parameter that leaves an instantiation's body and kernel arguments as they were does not disturb it; a kernel argument added to it, or a step of its body moved
+// into a helper, does (profiles/r24_rmsfold_kernels.txt; DESIGN.md §4, "The RMS row kernels on one template").
 #pragma once
 #include <initializer_list>
 
@@ -45,13 +49,104 @@ __device__ __forceinline__ void pin_before_loads(v4u (&sv)[VPT]) {
 // before any use)
 __device__ __forceinline__ int64_t clamped_vec_off(int idx, int nvec) { return (int64_t)(idx < nvec ? idx : nvec - 1) * 16; }
 
-// K1n / K1a (QSPEC A1, N1-N6, Q1-Q6).  Reads x (and the residual) once and the weight vector from cache, writes 1 B/elem + 4 B/row (+ the sum, + h when asked for).
-// Registers at 16 vectors, ADD: x + residual + weight in flight (192), then sum + weight + h (192) — the plain kernel's budget.
-template <int DT, int VPT, int TPR, bool WRITE_H, bool ADD>
-__global__ __launch_bounds__(256) void rmsnorm_quant_rows(row_in_bytes<ADD> x, int64_t ldx_bytes, const uint8_t* res, int64_t ldr_bytes, uint8_t* sum_out,
+// ---------------------------------------------------------------------------------------------------------------- the gains of the RMS norms
+// What a norm does with x * rs and the weight, as a tag of the row kernels: h_vec on one 16-byte vector (two elements per instruction), h on one element (the caller
+// rounds to the storage dtype).  A tag leaves the instructions of the instantiations that existed before it as they were (profiles/r24_rmsfold_kernels.txt).
+// N5 (Llama): x * rs is rounded to the storage dtype BEFORE the gain w
+struct LlamaGain {
+    template <int DT> __device__ static __forceinline__ float h(float x, float w, float rs) { return rms_h<DT>(x, w, rs); }
+    template <int DT> __device__ static __forceinline__ v4u h_vec(const v4u& xv, const v4u& wv, float rs) { return rms_h_vec<DT>(xv, wv, rs); }
+};
+// NG5 (Gemma, PLUS_ONE) and NO5 (OLMo): h = (x * rs) * g with g = 1 + w or w, every operation rounded in binary32 (the build has no contraction) and ONE storage
+// rounding.  GemmaRMSNorm is ((x.float() * rs) * (1 + w.float())).type_as(x); OLMo's is the same without the `1 +`.
+template <bool PLUS_ONE>
+struct OneRoundingGain {
+    template <int DT> __device__ static __forceinline__ float h(float x, float w, float rs) {
+        const float g = PLUS_ONE ? 1.0f + w : w;
+        return (x * rs) * g;
+    }
+    template <int DT> __device__ static __forceinline__ v4u h_vec(const v4u& xv, const v4u& wv, float rs) {
+        v4u out;
+        if constexpr (DT == PQ_F32) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t xb = xv[j], wb = wv[j];      // copies first (hipcc quirk with vector-element lvalues)
+                out[j] = __builtin_bit_cast(uint32_t, h<DT>(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, wb), rs));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t xw = xv[j], ww = wv[j];
+                if constexpr (PLUS_ONE) {
+                    const v2f g = splat(1.0f) + Pair<DT>::unpack(ww);
+                    out[j] = Pair<DT>::pack((Pair<DT>::unpack(xw) * splat(rs)) * g);
+                } else {
+                    out[j] = Pair<DT>::pack((Pair<DT>::unpack(xw) * splat(rs)) * Pair<DT>::unpack(ww));          // (the gain unpacked AFTER the product: hipcc keeps the order)
+                }
+            }
+        }
+        return out;
+    }
+};
+struct GemmaGain : OneRoundingGain<true> {};
+struct OlmoGain : OneRoundingGain<false> {};
+
+// ---------------------------------------------------------------------------------------------------------------- the steps of a row kernel
+// A step is a __forceinline__ function here only where a kernel that calls it compiles to the instructions it had with the step written out: hipcc schedules and
+// allocates an inlined helper differently from the same statements in the kernel.  The two below are K1pang's.  rmsnorm_quant_rows, olmo_postnorm_rows and the
+// first halves of the post-norm kernels keep their steps written out: DESIGN.md §4, "The RMS row kernels on one template", has what was tried and how many kernels
+// each step changed.
+// this lane's share of the sum of squares of a row held in registers (N2: vectors in increasing v, elements in order; slots past the row are zeroed first:
+// fma(0, 0, acc) = acc), one accumulator per 64-lane group of the specification ("Row layouts")
+template <int DT, int VPT, int TPR>
+__device__ __forceinline__ void lane_sumsq(v4u (&sv)[VPT], int t, int nvec, float (&acc)[TPR == 64 ? 4 : 1]) {
+    constexpr int EPV = 16 / Elem<DT>::kBytes;
+    constexpr int NACC = TPR == 64 ? 4 : 1;
+#pragma unroll
+    for (int gi = 0; gi < NACC; ++gi) acc[gi] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        if (i * TPR + t >= nvec) sv[i] = v4u{0u, 0u, 0u, 0u};
+        float f[EPV];
+        Unpack<DT, EPV>::run(sv[i], f);
+#pragma unroll
+        for (int j = 0; j < EPV; ++j) acc[i & (NACC - 1)] = __builtin_fmaf(f[j], f[j], acc[i & (NACC - 1)]);
+    }
+}
+
+// the row's sum from the lanes' accumulators (N3).  One wave per row: row_sum<64>'s butterfly with its loops written out, as K1pang always had it
+template <int TPR>
+__device__ __forceinline__ float rms_row_sum(float (&acc)[TPR == 64 ? 4 : 1]) {
+    if constexpr (TPR == 64) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int gi = 0; gi < 4; ++gi) acc[gi] = acc[gi] + __shfl_xor(acc[gi], off, 64);
+        }
+        return ((acc[0] + acc[1]) + acc[2]) + acc[3];
+    } else {
+        return rms_block_sum(acc[0]);
+    }
+}
+
+// the value of a kernel's optional multiplier argument (a pack of no or one float)
+__device__ __forceinline__ float the_multiplier(float m) { return m; }
+
+// K1n / K1a, K1ng / K1ang, K1ma / K1mo (QSPEC S1, A1, N1-N6 or NG1-NG6, Q1-Q6).  Reads x (and the residual) once and the weight vector from cache, writes 1 B/elem +
+// 4 B/row (+ the sum, + h when asked for).  Registers at 16 vectors, ADD: x + residual + weight in flight (192), then sum + weight + h (192) — the plain kernel's budget.
+// GAIN: what the norm does with x * rs and the weight.  MULT: empty, or `float` — then the kernel takes `float mult` after ldr_bytes and adds cast(x * mult) (S1) in x's
+// place: the product takes the place of x before the add, so nothing more is live at the peak.  !QUANT: the add-only form, which stops after storing the sum (wgt, q,
+// scale and h_out are null and never touched).  An argument that exists only in the instantiations that use it leaves the others their kernel arguments, and every
+// instantiation the instructions it had as gemma_rmsnorm_quant_rows / scaled_add_rmsnorm_quant_rows or before GAIN, QUANT and MULT existed (profiles/r24_rmsfold_kernels.txt).
+template <int DT, int VPT, int TPR, bool WRITE_H, bool ADD, class GAIN = LlamaGain, bool QUANT = true, class... MULT>
+__global__ __launch_bounds__(256) void rmsnorm_quant_rows(row_in_bytes<ADD> x, int64_t ldx_bytes, const uint8_t* res, int64_t ldr_bytes, MULT... mult, uint8_t* sum_out,
                                                           int64_t lds_bytes, const uint8_t* __restrict__ wgt, float eps, int cols, int nvec, int64_t rows,
                                                           int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale, uint8_t* __restrict__ h_out,
                                                           int64_t ldh_bytes) {
+    constexpr bool SCALED = sizeof...(MULT) == 1;
+    static_assert((SCALED || sizeof...(MULT) == 0) && (std::is_same_v<MULT, float> && ...), "MULT is empty or one float");
+    static_assert(ADD || (QUANT && !SCALED), "the multiplier scales x in front of the add, and the add-only form stores the sum alone");
+    static_assert(QUANT || !WRITE_H, "h is the normalised sum: the add-only form has none");
     constexpr int EPV = 16 / Elem<DT>::kBytes;
     constexpr int NACC = TPR == 64 ? 4 : 1;
     const int t = TPR == 256 ? threadIdx.x : threadIdx.x & 63;
@@ -71,8 +166,19 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_rows(row_in_bytes<ADD> x, i
             rv[i] = *reinterpret_cast<const v4u*>(rr + off);
         }
 #pragma unroll
-        for (int i = 0; i < VPT; ++i) sv[i] = add_vec<DT>(sv[i], rv[i]);          // A1: the sum takes the place of x
-        pin_before_loads(sv);
+        for (int i = 0; i < VPT; ++i) {
+            if constexpr (SCALED) sv[i] = add_vec<DT>(scale_vec<DT>(sv[i], the_multiplier(mult...)), rv[i]);          // S1, then A1
+            else sv[i] = add_vec<DT>(sv[i], rv[i]);                                                                   // A1: the sum takes the place of x
+        }
+        if constexpr (QUANT) pin_before_loads(sv);
+    }
+    if constexpr (!QUANT) {
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+            const int idx = i * TPR + t;
+            if (active && idx < nvec) store_wt_b128(sum_out + row * lds_bytes + (int64_t)idx * 16, sv[i]);
+        }
+        return;
     }
     // the weight row (shared by every workgroup: cache-resident).  Plain: with x, every load before the first use.  ADD: asked for once the residual's registers
     // are free, and BEFORE the stores of the sum, so that waiting for it does not wait for them
@@ -119,8 +225,9 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_rows(row_in_bytes<ADD> x, i
     for (int i = 0; i < VPT; ++i) {
         const int idx = i * TPR + t;
         // a slot past the row holds a duplicate of the weight's last vector and rs may be Inf or NaN: its h is zero, not 0 * Inf = NaN (which would be the row's
-        // amax).  Zeroed AFTER the arithmetic, as gemma_rmsnorm_quant_rows does (profiles/r22_k1n_dead_slots.txt has the registers and the times of both forms)
-        hv[i] = rms_h_vec<DT>(sv[i], wv[i], rs);
+        // amax).  Zeroed AFTER the arithmetic: selecting before it costs K1ng's 4-vector wave layout four VGPRs and a wave per SIMD (profiles/r22_k1n_dead_slots.txt has
+        // the registers and the times of both forms)
+        hv[i] = GAIN::template h_vec<DT>(sv[i], wv[i], rs);
         if (idx >= nvec) hv[i] = v4u{0u, 0u, 0u, 0u};
         ab = vec_amax_bits<DT>(hv[i], ab);
         if constexpr (WRITE_H) {
@@ -248,27 +355,36 @@ __device__ __forceinline__ void generic_amax_and_encode(int64_t row, int64_t col
 
 // ADD: every pass walks the elements in the SAME thread order, so a thread only ever reads back the sums it stored itself: the first pass reads x and the residual
 // and stores s, the others start from the stored s and never touch x or the residual again (either of them may BE sum_out).
-template <int DT, bool ADD>
-__global__ __launch_bounds__(256) void rmsnorm_quant_generic(row_in_void<ADD> x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds,
+template <int DT, bool ADD, class GAIN = LlamaGain, bool QUANT = true, class... MULT>
+__global__ __launch_bounds__(256) void rmsnorm_quant_generic(row_in_void<ADD> x, int64_t ldx, const void* res, int64_t ldr, MULT... mult, void* sum_out, int64_t lds,
                                                              const void* __restrict__ wgt, float eps, int64_t cols, int8_t* __restrict__ q, int64_t ldq,
                                                              float* __restrict__ scale, void* __restrict__ h_out, int64_t ldh) {
+    constexpr bool SCALED = sizeof...(MULT) == 1;
+    static_assert(ADD || (QUANT && !SCALED), "the multiplier scales x in front of the add, and the add-only form stores the sum alone");
     using S = typename Elem<DT>::store_t;
     const int64_t row = blockIdx.x;
     const S* xr = reinterpret_cast<const S*>(x) + row * ldx;
     const S* rr = reinterpret_cast<const S*>(res) + row * ldr;
     S* sr = reinterpret_cast<S*>(sum_out) + row * lds;
-    const S* wr = reinterpret_cast<const S*>(wgt);
-    const S* in = ADD ? sr : xr;            // what is normalised
     float acc = 0.0f;
     walk_row<DT, true>(cols, [&](int64_t c) {
-        const S s = ADD ? add_elem<DT>(rr[c], xr[c]) : xr[c];
+        S s;
+        if constexpr (SCALED) s = add_elem<DT>(rr[c], scale_elem<DT>(xr[c], the_multiplier(mult...)));          // S1, A1
+        else s = ADD ? add_elem<DT>(rr[c], xr[c]) : xr[c];
         if constexpr (ADD) sr[c] = s;
-        const float f = Elem<DT>::to_f32(s);
-        acc = __builtin_fmaf(f, f, acc);
+        if constexpr (QUANT) {
+            const float f = Elem<DT>::to_f32(s);
+            acc = __builtin_fmaf(f, f, acc);
+        }
     });
-    const float rs = rms_rs(rms_block_sum(acc), (int)cols, eps);
-    generic_amax_and_encode<DT, ADD>(
-        row, cols, [&](int64_t c) -> S { return Elem<DT>::from_f32(rms_h<DT>(Elem<DT>::to_f32(in[c]), Elem<DT>::to_f32(wr[c]), rs)); }, q, ldq, scale, h_out, ldh);
+    if constexpr (QUANT) {
+        const S* wr = reinterpret_cast<const S*>(wgt);
+        const S* in = ADD ? sr : xr;            // what is normalised
+        const float rs = rms_rs(rms_block_sum(acc), (int)cols, eps);
+        generic_amax_and_encode<DT, ADD>(
+            row, cols, [&](int64_t c) -> S { return Elem<DT>::from_f32(GAIN::template h<DT>(Elem<DT>::to_f32(in[c]), Elem<DT>::to_f32(wr[c]), rs)); }, q, ldq, scale, h_out,
+            ldh);
+    }
 }
 
 // the row is read three times (from cache after the first)
@@ -355,6 +471,53 @@ static void rownorm_dispatch(std::initializer_list<RowOperand> operands, int64_t
     };
     if (wave) with_vpt(std::integral_constant<int, 64>{});
     else with_vpt(std::integral_constant<int, 256>{});
+}
+
+// the three explicit instantiations of a dispatcher that pq_launch.h declares per dtype; the signature is that declaration's
+#define PQ_INSTANTIATE_DTYPES(fn)                     \
+    template decltype(fn<PQ_BF16>) fn<PQ_BF16>;       \
+    template decltype(fn<PQ_FP16>) fn<PQ_FP16>;       \
+    template decltype(fn<PQ_F32>) fn<PQ_F32>;
+
+// an operand as the row kernels take it: its base as bytes (the leading dimension goes with it, times Elem<DT>::kBytes)
+static inline const uint8_t* row_bytes(const void* p) { return reinterpret_cast<const uint8_t*>(p); }
+static inline uint8_t* row_bytes(void* p) { return reinterpret_cast<uint8_t*>(p); }
+
+// rownorm_dispatch for an entry whose quantisation group (weight, q, scale, h_out) is absent as a whole in its add-only form (pq_api.hip refuses a partly-null
+// group): launch and generic get QUANT as one more integral constant in front of the grid, and the add-only form has no h_out
+template <int DT, class Launch, class Generic>
+static void rownorm_dispatch_quant_or_sum(std::initializer_list<RowOperand> operands, int64_t rows, int64_t cols, bool quant, const int8_t* q, int64_t ldq,
+                                          const void* h_out, int64_t ldh, Launch&& launch, Generic&& generic) {
+    rownorm_dispatch<DT>(
+        operands, rows, cols, quant ? q : nullptr, quant ? ldq : 0, quant ? h_out : nullptr, quant ? ldh : 0,
+        [&](auto vpt, auto tpr, auto write_h, dim3 grid, int nvec) {
+            if (quant) launch(vpt, tpr, write_h, std::true_type{}, grid, nvec);
+            else if constexpr (!decltype(write_h)::value) launch(vpt, tpr, write_h, std::false_type{}, grid, nvec);
+        },
+        [&](dim3 grid) {
+            if (quant) generic(std::true_type{}, grid);
+            else generic(std::false_type{}, grid);
+        });
+}
+
+// K1n / K1a / K1ng / K1ang / K1ma: the dispatch of rmsnorm_quant_rows / rmsnorm_quant_generic<.., ADD, GAIN, QUANT, MULT...> (!ADD: res and sum_out are null, their
+// leading dimensions 0).  SUM_ONLY_FORM: the entry has an add-only form, wgt == nullptr (K1mo), and its object the kernels of it; mult: the multiplier of K1ma / K1mo
+template <int DT, bool ADD, class GAIN, bool SUM_ONLY_FORM = false, class... MULT>
+static void rmsnorm_rows_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, void* sum_out, int64_t lds, const void* wgt, float eps, int64_t rows,
+                                  int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st, MULT... mult) {
+    const int64_t kb = Elem<DT>::kBytes;
+    rownorm_dispatch_quant_or_sum<DT>(
+        {{x, ldx}, {res, ldr}, {sum_out, lds}, {wgt, 0}}, rows, cols, !SUM_ONLY_FORM || wgt != nullptr, q, ldq, h_out, ldh,
+        [&](auto vpt, auto tpr, auto write_h, auto quant, dim3 grid, int nvec) {
+            constexpr bool QUANT = !SUM_ONLY_FORM || decltype(quant)::value;
+            rmsnorm_quant_rows<DT, decltype(vpt)::value, decltype(tpr)::value, decltype(write_h)::value, ADD, GAIN, QUANT, MULT...><<<grid, dim3(256), 0, st>>>(
+                row_bytes(x), ldx * kb, row_bytes(res), ldr * kb, mult..., row_bytes(sum_out), lds * kb, row_bytes(wgt), eps, (int)cols, nvec, rows, q, ldq, scale,
+                row_bytes(h_out), ldh * kb);
+        },
+        [&](auto quant, dim3 grid) {
+            constexpr bool QUANT = !SUM_ONLY_FORM || decltype(quant)::value;
+            rmsnorm_quant_generic<DT, ADD, GAIN, QUANT, MULT...><<<grid, dim3(256), 0, st>>>(x, ldx, res, ldr, mult..., sum_out, lds, wgt, eps, cols, q, ldq, scale, h_out, ldh);
+        });
 }
 
 }  // namespace pq

@@ -13,6 +13,7 @@ import torch
 
 from tests import addlnorm_spec as AL
 from tests import lnorm_spec as LS
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = "pq_add_layernorm_quant_rowwise"
@@ -140,26 +141,7 @@ def test_spec_is_the_add_then_the_layernorm_spec():
 
 
 def _kernels_of(objname):
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, objname + ".o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in (objname + ".altest.fatbin", objname + ".altest.co", ".unused." + objname + ".altest.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
-    for f in (fat, co, unused):
-        os.remove(f)
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count|agpr_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return kernels, dis
+    return kernels_of(objname, disassembly=True)
 
 
 FORBIDDEN = re.compile(r"\bs_\w*(store|atomic|dcache)\w*|\bscratch_", re.I)          # no scalar instruction that writes memory or touches the scalar data cache, no scratch

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import addnorm_spec as A
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = "pq_add_rmsnorm_quant_rowwise"
@@ -142,37 +143,18 @@ def test_spec_is_the_add_then_the_oracle():
 
 
 def test_code_object_has_every_layout_and_no_scratch():
-    """as `make spillcheck` reads the GEMM objects: rmsnorm_quant_rows<.., 64 | 256, .., ADD = true> / rmsnorm_quant_generic<.., true> for all three dtypes, with and
+    """as `make spillcheck` reads the GEMM objects: rmsnorm_quant_rows<.., 64 | 256, .., ADD = true, LlamaGain, QUANT = true> / rmsnorm_quant_generic<.., true, LlamaGain, true> (no multiplier argument) for all three dtypes, with and
     without h_out, none with scratch or spills"""
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, "addnorm_kernels.o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in ("addnorm_kernels.test.fatbin", "addnorm_kernels.test.co", ".unused.addnorm.test.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                   check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    kernels, dis = kernels_of("addnorm_kernels", disassembly=True)
     for dt in range(3):
         # wave: 1, 2, 4, 8 vectors per lane; vec: 1, 2, 4, 8, 16 per thread; each with and without h_out; one generic kernel
-        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb1EE" % dt, k)]) == 4 * 2, dt
-        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb1EE" % dt, k)]) == 5 * 2, dt
-        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_genericILi%dELb1EE" % dt, k)]) == 1, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb1ENS_9LlamaGainELb1EJEEE" % dt, k)]) == 4 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb1ENS_9LlamaGainELb1EJEEE" % dt, k)]) == 5 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_genericILi%dELb1ENS_9LlamaGainELb1EJEEE" % dt, k)]) == 1, dt
     assert len(kernels) == 3 * (8 + 10 + 1)
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
     assert "global_load_dwordx4" in dis and "global_store_dwordx4" in dis and "v_pk_add_f32" in dis and "scratch_" not in dis
-    for f in (fat, co, unused):
-        os.remove(f)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the decoder-layer probe

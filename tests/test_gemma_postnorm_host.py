@@ -185,8 +185,9 @@ def test_python_entries_have_no_cpu_fallback_and_check_their_operands():
 def test_postnorm_object_holds_every_layout_without_scratch():
     """every instantiation the dispatch can launch is in gemma_postnorm_kernels.o — K1pang with and without h_out and K1pa, at every row layout, and the two generic
     kernels per dtype — and none uses scratch or spills; the objects of the existing Gemma norm kernels hold none of them"""
-    from tests.test_gemma_spec_host import _kernels_of, _no_scratch_no_spills
-    k = _kernels_of("gemma_postnorm_kernels")
+    from tests.code_objects import kernels_of
+    from tests.test_gemma_spec_host import _no_scratch_no_spills
+    k = kernels_of("gemma_postnorm_kernels", must_be_built=True)
     for dt in range(3):
         for wh, qn in ("01", "11", "00"):          # (WRITE_H, QUANT)
             for v in (1, 2, 4, 8):                 # one wave per row: 1, 2, 4, 8 vectors per lane
@@ -198,4 +199,4 @@ def test_postnorm_object_holds_every_layout_without_scratch():
     assert len(k) == 3 * (3 * 9 + 2)
     _no_scratch_no_spills(k)
     for obj in ("gemma_norm_kernels", "add_gemma_norm_kernels"):
-        assert not [n for n in _kernels_of(obj) if "postnorm" in n], obj
+        assert not [n for n in kernels_of(obj, must_be_built=True) if "postnorm" in n], obj

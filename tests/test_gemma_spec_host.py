@@ -13,6 +13,7 @@ import torch
 
 from tests import act_spec as U
 from tests import gemma_spec as G
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = {"pq_gemma_rmsnorm_quant_rowwise": ["x", "ld_x", "weight", "eps", "dtype", "rows", "cols", "q", "ld_q", "scale", "h_out", "ld_h", "stream"],
@@ -220,26 +221,7 @@ def test_python_entries_have_no_cpu_fallback_and_check_their_operands():
 
 # ---------------------------------------------------------------------------------------------------------------- the code objects
 def _kernels_of(objname):
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, objname + ".o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the ROCm LLVM tools")
-    assert os.path.exists(obj), f"{obj} was not built"
-    fat, co, unused = (os.path.join(build, f) for f in (objname + ".gemmatest.fatbin", objname + ".gemmatest.co", ".unused." + objname + ".gemmatest.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    for f in (fat, co, unused):
-        os.remove(f)
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return kernels
+    return kernels_of(objname, must_be_built=True)
 
 
 def _no_scratch_no_spills(kernels):
@@ -254,10 +236,10 @@ def test_norm_objects_hold_every_layout_without_scratch(obj, add):
     for dt in range(3):
         for wh in "01":
             for v in (1, 2, 4, 8):          # one wave per row: 1, 2, 4, 8 vectors per lane
-                assert len([n for n in k if re.search(r"\d+gemma_rmsnorm_quant_rowsILi%dELi%dELi64ELb%sELb%dEE" % (dt, v, wh, add), n)]) == 1, (dt, v, wh)
+                assert len([n for n in k if re.search(r"\d+rmsnorm_quant_rowsILi%dELi%dELi64ELb%sELb%dENS_9GemmaGainELb1EJEEE" % (dt, v, wh, add), n)]) == 1, (dt, v, wh)
             for v in (1, 2, 4, 8, 16):      # 256 threads per row: 1 .. 16 vectors per thread
-                assert len([n for n in k if re.search(r"\d+gemma_rmsnorm_quant_rowsILi%dELi%dELi256ELb%sELb%dEE" % (dt, v, wh, add), n)]) == 1, (dt, v, wh)
-        assert len([n for n in k if re.search(r"\d+gemma_rmsnorm_quant_genericILi%dELb%dEE" % (dt, add), n)]) == 1, dt
+                assert len([n for n in k if re.search(r"\d+rmsnorm_quant_rowsILi%dELi%dELi256ELb%sELb%dENS_9GemmaGainELb1EJEEE" % (dt, v, wh, add), n)]) == 1, (dt, v, wh)
+        assert len([n for n in k if re.search(r"\d+rmsnorm_quant_genericILi%dELb%dENS_9GemmaGainELb1EJEEE" % (dt, add), n)]) == 1, dt
     assert len(k) == 3 * (8 + 10 + 1)
     _no_scratch_no_spills(k)
 
@@ -297,6 +279,6 @@ def test_k1s_object_holds_exactly_the_layouts_of_the_dispatchers_ladder():
 @pytest.mark.parametrize("obj,count", [("producer_kernels", None), ("addnorm_kernels", 57), ("act_kernels", None), ("glu_kernels", None)])
 def test_the_existing_objects_hold_no_kernel_of_the_new_family(obj, count):
     k = _kernels_of(obj)
-    assert k and not [n for n in k if re.search(r"gemma_rmsnorm_quant|gelu_mul_quant|GegluOp", n)], obj
+    assert k and not [n for n in k if re.search(r"GemmaGain|gelu_mul_quant|GegluOp", n)], obj
     if count is not None:
         assert len(k) == count

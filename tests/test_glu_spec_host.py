@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from oracle import qspec_numpy as Q
 from tests import glu_spec as G
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TD = {0: torch.bfloat16, 1: torch.float16, 2: torch.float32}
@@ -163,30 +164,11 @@ def test_python_entry_point_has_no_cpu_fallback():
 
 def test_glu_code_object_has_no_scratch_and_the_expected_kernels():
     """as `make spillcheck` reads the GEMM objects: no scratch, no VGPR / SGPR spill in any kernel of glu_kernels.o, every row layout of both kinds is there"""
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, "glu_kernels.o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in ("glu_kernels.test.fatbin", "glu_kernels.test.co", ".unused.glu.test.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                   check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    kernels, dis = kernels_of("glu_kernels", disassembly=True)
     # 3 dtypes x 2 kinds x with / without h_out x (one wave per row: 1, 2, 4 vectors | 256 threads: 1, 2, 4, 8, 16 | 512 threads: 3)
     assert len([k for k in kernels if "rowmap_quant_rowsINS_5GluOp" in k]) == 3 * 2 * 2 * 9
     assert len([k for k in kernels if "rowmap_quant_genericINS_5GluOp" in k]) == 3 * 2
     assert len([k for k in kernels if "glu_short_check" in k]) == 2 * 2
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
     assert "global_load_dwordx4" in dis and "v_med3_f32" in dis and "v_cmp_u_f32" in dis and "v_rcp_f32" in dis and "v_div_scale_f32" in dis
-    for f in (fat, co, unused):
-        os.remove(f)

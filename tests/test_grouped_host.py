@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 import torch
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("pq_qlinear_s8_grouped", "pq_gemm_s8s8s32_grouped", "pq_grouped_variant_name")
@@ -131,29 +132,9 @@ def test_route_plan_and_combine_against_brute_force(T, k, E, seed):
 
 def test_grouped_code_object_is_the_hand_written_tile():
     """as `make spillcheck` reads it: no scratch, no VGPR spill in any gemm_s8_grouped instantiation; and the tile's own instructions are there"""
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, "gemm_s8_grouped.o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co = os.path.join(build, "gemm_s8_grouped.test.fatbin"), os.path.join(build, "gemm_s8_grouped.test.co")
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, os.path.join(build, ".unused.test.o")], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                   check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    kernels = {}
-    name = None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    kernels, dis = kernels_of("gemm_s8_grouped", disassembly=True)
     grouped = {k: v for k, v in kernels.items() if "gemm_s8_grouped" in k}
     assert len(grouped) == 16, sorted(grouped)            # 4 output kinds x 2 tiles x with / without the row index
     for k, v in grouped.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0, (k, v)
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
     assert "global_load_lds_dwordx4" in dis and "v_mfma_i32_16x16x64_i8" in dis
-    for f in (fat, co, os.path.join(build, ".unused.test.o")):
-        os.remove(f)

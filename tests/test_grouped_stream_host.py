@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 import torch
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("pq_qlinear_s8_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", "pq_grouped_stream_plan_name")
@@ -167,31 +168,7 @@ def test_grouped_qlinear_picks_its_entry_from_the_row_count(monkeypatch):
 
 
 def _kernel_notes():
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    obj = os.path.join(ROOT, "protoquant_amd", "csrc", "build", "gemm_s8_grouped_stream.o")
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "llvm-readelf"))):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    tmp = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    fat, co = os.path.join(tmp, ".gs_host_test.fatbin"), os.path.join(tmp, ".gs_host_test.co")
-    try:
-        subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, os.path.join(tmp, ".gs_host_test.unused.o")], check=True)
-        subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                       check=True)
-        notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    finally:
-        for f in (fat, co, os.path.join(tmp, ".gs_host_test.unused.o")):
-            if os.path.exists(f):
-                os.remove(f)
-    kernels, name = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*\.name:\s+(\S+)", line)
-        if m:
-            name = m.group(1)
-            continue
-        m = re.match(r"\s*\.(private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\d+)", line)
-        if m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return {k: v for k, v in kernels.items() if "gemm_s8_grouped_stream" in k}
+    return {k: v for k, v in kernels_of("gemm_s8_grouped_stream").items() if "gemm_s8_grouped_stream" in k}
 
 
 def test_code_object_holds_every_reachable_instantiation_without_scratch_or_spills():

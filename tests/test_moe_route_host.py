@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 import torch
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine")
@@ -120,30 +121,13 @@ def test_python_entry_points_have_no_cpu_fallback():
 def test_moe_code_object_has_no_scratch_and_the_expected_kernels():
     """as `make spillcheck` reads the GEMM objects: no scratch, no VGPR spill in any kernel of moe_kernels.o; both forms of the routing and every layout of the combine are
     there; and no single-rounding mixed-precision instruction stands in for the two roundings of the combine"""
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, "moe_kernels.o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in ("moe_kernels.test.fatbin", "moe_kernels.test.co", ".unused.moe.test.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                   check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    kernels, dis = kernels_of("moe_kernels", disassembly=True)
     assert len([k for k in kernels if "moe_route_rank" in k]) == 4          # int32 / int64 ids x one-launch / three-launch form
     assert len([k for k in kernels if "moe_route_count" in k]) == 2
     assert len([k for k in kernels if "moe_route_scan" in k]) == 1
     assert len([k for k in kernels if "moe_combine_kernel" in k]) == 12     # 3 dtypes x (wave | workgroup per token) x (16-byte | element-wise rows)
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
     assert "global_load_dwordx4" in dis and "global_store_dwordx4" in dis
     body, cur = {}, None                                                   # disassembly per kernel
     for ln in dis.splitlines():
@@ -158,5 +142,3 @@ def test_moe_code_object_has_no_scratch_and_the_expected_kernels():
         assert "v_mul_f32" in text or "v_pk_mul_f32" in text, k
         for bad in ("v_fma", "v_mad_mix", "v_fmac", "v_pk_fma", "v_mad_f32", "v_mac_f32", "v_pk_mul_f16", "v_pk_add_f16", "v_dot"):
             assert bad not in text, f"{bad} in {k}: the combine is one binary32 multiply and one binary32 add, each rounded on its own"
-    for f in (fat, co, unused):
-        os.remove(f)

@@ -136,8 +136,9 @@ def test_python_entries_have_no_cpu_fallback_and_check_their_operands():
 def test_olmo_object_holds_every_layout_without_scratch():
     """every instantiation the dispatch can launch is in olmo_postnorm_kernels.o — K1oq, K1oa and K1on at every row layout, and the three generic kernels per dtype — and
     none uses scratch or spills; the objects of the Gemma post-norm and of the Llama add-norm hold none of them"""
-    from tests.test_gemma_spec_host import _kernels_of, _no_scratch_no_spills
-    k = _kernels_of("olmo_postnorm_kernels")
+    from tests.code_objects import kernels_of
+    from tests.test_gemma_spec_host import _no_scratch_no_spills
+    k = kernels_of("olmo_postnorm_kernels", must_be_built=True)
     for dt in range(3):
         for form in ("11", "10", "00"):            # (ADD, QUANT)
             for v in (1, 2, 4, 8):                 # one wave per row: 1, 2, 4, 8 vectors per lane
@@ -148,4 +149,4 @@ def test_olmo_object_holds_every_layout_without_scratch():
     assert len(k) == 3 * 3 * (9 + 1)
     _no_scratch_no_spills(k)
     for obj in ("gemma_postnorm_kernels", "addnorm_kernels"):
-        assert not [n for n in _kernels_of(obj) if "olmo" in n], obj
+        assert not [n for n in kernels_of(obj, must_be_built=True) if "olmo" in n], obj

@@ -14,6 +14,7 @@ import torch
 from tests import add2lnorm_spec as A2
 from tests import lnorm_spec as LS
 from tests.addnorm_spec import add_a1
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = "pq_parallel_layernorm_quant_rowwise"
@@ -172,30 +173,10 @@ def test_the_association_is_visible_on_the_gpu_tests_inputs(dtype):
             assert frac >= 0.10, (dtype, rows, cols, name, frac)
 
 
-def _kernels_of(objname):
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, objname + ".o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in (objname + ".pltest.fatbin", objname + ".pltest.co", ".unused." + objname + ".pltest.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    for f in (fat, co, unused):
-        os.remove(f)
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|vgpr_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return kernels
 
 
 def test_code_object_has_every_layout_of_the_three_forms_and_no_scratch():
-    k = _kernels_of("parallel_layernorm_kernels")
+    k = kernels_of("parallel_layernorm_kernels")
     forms = (("b1", 1), ("b1", 2), ("b0", 2))          # (ADD2, NORMS): K1pl with one norm, with two, K1l2 — and never the plain K1l
     for dt in range(3):
         for add, norms in forms:

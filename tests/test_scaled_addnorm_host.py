@@ -17,6 +17,7 @@ import torch
 from protoquant_amd.qtensor import scaled_add, scaled_add_rmsnorm_quantize  # noqa: F401  (the ops this file is about)
 from tests import addnorm_spec as A
 from tests import scaled_addnorm_spec as S
+from tests.code_objects import kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = "pq_scaled_add_rmsnorm_quant_rows"
@@ -236,36 +237,17 @@ def test_python_entries_refuse_mismatched_operands():
 
 # ---------------------------------------------------------------------------------------------------------------- the code object
 def test_code_object_has_every_layout_and_no_scratch():
-    """as tests/test_addnorm_host.py reads K1a's object: scaled_add_rmsnorm_quant_rows<.., 64 | 256, WRITE_H, QUANT> / scaled_add_rmsnorm_quant_generic<.., QUANT> for all
-    three dtypes — K1ma with and without h_out, K1mo without — none with scratch or spills, and no single-rounding fp16 convert"""
-    build = os.path.join(ROOT, "protoquant_amd", "csrc", "build")
-    obj = os.path.join(build, "scaled_addnorm_kernels.o")
-    llvm = os.environ.get("LLVMBIN", "/opt/rocm/lib/llvm/bin")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-readelf")):
-        pytest.skip("needs the built object and the ROCm LLVM tools")
-    fat, co, unused = (os.path.join(build, f) for f in ("scaled_addnorm_kernels.test.fatbin", "scaled_addnorm_kernels.test.co", ".unused.scaled_addnorm.test.o"))
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, unused], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                   check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    kernels, name = {}, None
-    for ln in notes.splitlines():
-        m = re.search(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\S+)", ln)
-        if m and m.group(1) == "name":
-            name = m.group(2)
-        elif m and name:
-            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    """as tests/test_addnorm_host.py reads K1a's object: rmsnorm_quant_rows<.., 64 | 256, WRITE_H, ADD = true, LlamaGain, QUANT, float> / rmsnorm_quant_generic<.., true, LlamaGain, QUANT,
+    float> (the instantiations that take the multiplier) for all three dtypes — K1ma with and without h_out, K1mo without — none with scratch or spills, and no single-rounding fp16 convert"""
+    kernels, dis = kernels_of("scaled_addnorm_kernels", disassembly=True)
     for dt in range(3):
         # wave: 1, 2, 4, 8 vectors per lane; 256 threads: 1, 2, 4, 8, 16 per thread; K1ma with and without h_out, K1mo without; one generic kernel each
-        assert len([k for k in kernels if re.search(r"scaled_add_rmsnorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb1EE" % dt, k)]) == 4 * 2, dt
-        assert len([k for k in kernels if re.search(r"scaled_add_rmsnorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb1EE" % dt, k)]) == 5 * 2, dt
-        assert len([k for k in kernels if re.search(r"scaled_add_rmsnorm_quant_rowsILi%dELi\d+ELi(64|256)ELb0ELb0EE" % dt, k)]) == 4 + 5, dt
-        assert len([k for k in kernels if re.search(r"scaled_add_rmsnorm_quant_genericILi%dELb[01]EE" % dt, k)]) == 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi64ELb[01]ELb1ENS_9LlamaGainELb1EJfEEE" % dt, k)]) == 4 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi256ELb[01]ELb1ENS_9LlamaGainELb1EJfEEE" % dt, k)]) == 5 * 2, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_rowsILi%dELi\d+ELi(64|256)ELb0ELb1ENS_9LlamaGainELb0EJfEEE" % dt, k)]) == 4 + 5, dt
+        assert len([k for k in kernels if re.search(r"\d+rmsnorm_quant_genericILi%dELb1ENS_9LlamaGainELb[01]EJfEEE" % dt, k)]) == 2, dt
     assert len(kernels) == 3 * (8 + 10 + 9 + 2)
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size", 1) == 0 and v.get("vgpr_spill_count", 1) == 0 and v.get("sgpr_spill_count", 1) == 0, (k, v)
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
     assert "global_load_dwordx4" in dis and "global_store_dwordx4" in dis and "v_pk_mul_f32" in dis and "v_pk_add_f32" in dis and "scratch_" not in dis
     assert "v_fma_mixlo" not in dis and "v_fma_mixhi" not in dis and "v_mad_mixlo" not in dis
-    for f in (fat, co, unused):
-        os.remove(f)
