@@ -269,6 +269,23 @@ int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const vo
 int32_t pq_scaled_add_rmsnorm_quant_rows(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, float multiplier, void* sum_out, int64_t ld_s, const void* weight,
                                          float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
 
+/* K1hn — the per-head RMSNorm of an attention's q and k (q_norm / k_norm of Qwen3, Qwen3-MoE, Gemma-3) in one launch; no codes, no scales (QSPEC HN1; DESIGN.md
+ * section 2).  The rows are heads of `cols` = head_dim elements, addressed by TWO strides, in elements, for x and for out:
+ *   out[o * ld_oo + i * ld_oi + c] = norm(x[o * ld_xo + i * ld_xi + c]; weight, eps)      o < n_outer, i < n_inner, c < cols
+ * so the q slice of a fused q/k/v output ([tokens, ld] x [heads, head_dim]) or a transposed view of it is normed where it lies.  weight: ONE [cols] of `dtype` for all
+ * rows.  gain: PQ_GAIN_LLAMA — N1-N5, cast_rne(f32(w) * f32(cast_rne(f32(x) * rs))), Qwen3RMSNorm; PQ_GAIN_GEMMA — NG1-NG5, cast_rne((f32(x) * rs) * (1 + f32(w))),
+ * Gemma3RMSNorm.  The bits are those h_out of pq_rmsnorm_quant_rowwise / pq_gemma_rmsnorm_quant_rowwise holds for the same rows.  Layouts (time only, never bits): a
+ * width of whole 16-byte vectors up to 1024 bytes with 16-byte aligned bases and strides packs 64 / G heads into a wave (G = the power of two >= cols * elem / 16, at
+ * least 4); anything else takes one wave per head, element by element.  No switch of its own.
+ * There is no in-place form: out may overlap neither x nor weight (told apart by their bounding ranges), and the rows of out may not overlap each other.  A null x /
+ * weight / out, a negative size or stride, n_outer * n_inner >= 2^31, cols >= 2^24, ld_xi < cols or ld_oi < cols where n_inner > 1, a negative or non-finite eps and an
+ * unknown gain or dtype are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.  n_outer * n_inner == 0 or cols == 0: nothing is read or
+ * written, returns PQ_OK. */
+#define PQ_GAIN_LLAMA 0
+#define PQ_GAIN_GEMMA 1
+int32_t pq_head_rmsnorm(const void* x, int64_t ld_xo, int64_t ld_xi, const void* weight, float eps, int32_t gain, int32_t dtype, int64_t n_outer, int64_t n_inner,
+                        int64_t cols, void* out, int64_t ld_oo, int64_t ld_oi, void* stream);
+
 /* K1gg— K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6

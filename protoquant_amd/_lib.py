@@ -15,6 +15,7 @@ ABI_VERSION = 1
 PQ_BF16, PQ_FP16, PQ_F32 = 0, 1, 2
 GLU_KINDS = {"clamped_silu": 0, "alpha_sigmoid": 1}        # PQ_GLU_* of include/pq_hip.h
 ACT_KINDS = {"relu": 0, "gelu_tanh": 1, "gelu_erf": 2}     # PQ_ACT_* of include/pq_hip.h
+GAIN_KINDS = {"llama": 0, "gemma": 1}                      # PQ_GAIN_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
 EXPORTS = (
@@ -35,6 +36,7 @@ EXPORTS = (
     "pq_gemma_postnorm_add_rmsnorm_quant_rowwise",
     "pq_olmo_postnorm_add_quant_rowwise",
     "pq_scaled_add_rmsnorm_quant_rows",
+    "pq_head_rmsnorm",
 )
 
 _lib = None
@@ -142,6 +144,8 @@ def lib() -> ctypes.CDLL:
     L.pq_olmo_postnorm_add_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp]
     L.pq_scaled_add_rmsnorm_quant_rows.restype = i32
     L.pq_scaled_add_rmsnorm_quant_rows.argtypes = [vp, i64, vp, i64, ctypes.c_float, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+    L.pq_head_rmsnorm.restype = i32
+    L.pq_head_rmsnorm.argtypes = [vp, i64, i64, vp, ctypes.c_float, i32, i32, i64, i64, i64, vp, i64, i64, vp]
     L.pq_gelu_mul_quant_rowwise.restype = i32
     L.pq_gelu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
     L.pq_set_option.restype = i32

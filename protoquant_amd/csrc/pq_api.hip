@@ -595,6 +595,53 @@ int32_t pq_olmo_postnorm_add_quant_rowwise(const void* x, int64_t ld_x, const vo
     return check_launch(fn);
 }
 
+// elements from the base of a two-stride operand of K1hn to the end of its last row; false: the product does not fit 64 bits
+static bool head_span(int64_t n_outer, int64_t ld_o, int64_t n_inner, int64_t ld_i, int64_t cols, int64_t* span) {
+    int64_t a, b;
+    if (__builtin_mul_overflow(n_outer - 1, ld_o, &a) || __builtin_mul_overflow(n_inner - 1, ld_i, &b) || __builtin_add_overflow(a, b, &a) ||
+        __builtin_add_overflow(a, cols, &a) || a > (INT64_MAX >> 2))
+        return false;
+    *span = a;
+    return true;
+}
+
+int32_t pq_head_rmsnorm(const void* x, int64_t ld_xo, int64_t ld_xi, const void* weight, float eps, int32_t gain, int32_t dtype, int64_t n_outer, int64_t n_inner,
+                        int64_t cols, void* out, int64_t ld_oo, int64_t ld_oi, void* stream) {
+    Range range_("pq:head_rmsnorm (K1hn)");
+    const char* fn = "pq_head_rmsnorm";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    if (gain != PQ_GAIN_LLAMA && gain != PQ_GAIN_GEMMA) return fail(PQ_ERR_BAD_ARG, "%s: unknown gain %d (0 = Llama: w * round(x * rs), 1 = Gemma: (x * rs) * (1 + w))", fn, gain);
+    if (n_outer < 0 || n_inner < 0) return fail(PQ_ERR_BAD_ARG, "%s: bad shape (n_outer=%lld n_inner=%lld)", fn, (long long)n_outer, (long long)n_inner);
+    if (n_outer > 0 && n_inner > 0 && n_outer > ((int64_t)INT32_MAX) / n_inner)
+        return fail(PQ_ERR_BAD_ARG, "%s: n_outer * n_inner must be < 2^31 (n_outer=%lld n_inner=%lld)", fn, (long long)n_outer, (long long)n_inner);
+    const int64_t heads = n_outer * n_inner, eb = dtype == PQ_F32 ? 4 : 2;
+    const struct { const char* name; int64_t ld; } lds[] = {{"ld_xo", ld_xo}, {"ld_xi", ld_xi}, {"ld_oo", ld_oo}, {"ld_oi", ld_oi}};
+    for (const auto& l : lds)
+        if (l.ld < 0) return fail(PQ_ERR_BAD_ARG, "%s: %s %lld < 0", fn, l.name, (long long)l.ld);
+    if (cols >= 0 && n_inner > 1 && ld_xi < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_xi %lld < cols %lld", fn, (long long)ld_xi, (long long)cols);
+    if (cols >= 0 && n_inner > 1 && ld_oi < cols) return fail(PQ_ERR_BAD_ARG, "%s: ld_oi %lld < cols %lld", fn, (long long)ld_oi, (long long)cols);
+    // the two-stride operands go to the shared checker as their bounding ranges (vectors of `span` elements): the shape, eps, the empty problem, the null pointers
+    // and the overlaps of out with x and with weight
+    int64_t span_x = 0, span_o = 0;
+    if (heads > 0 && cols > 0 && (!head_span(n_outer, ld_xo, n_inner, ld_xi, cols, &span_x) || !head_span(n_outer, ld_oo, n_inner, ld_oi, cols, &span_o)))
+        return fail(PQ_ERR_BAD_ARG, "%s: the strides do not fit 64-bit byte offsets (ld_xo=%lld ld_xi=%lld ld_oo=%lld ld_oi=%lld)", fn, (long long)ld_xo, (long long)ld_xi,
+                    (long long)ld_oo, (long long)ld_oi);
+    const RowOperand ops[] = {{"x", x, R_IN, nullptr, span_x, eb, ""}, {"weight", weight, R_IN, nullptr, cols, eb, ""}, {"out", out, R_OUT, nullptr, span_o, eb, ""}};
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, heads, cols, &eps, ops, 3, &empty); rc || empty) return rc;
+    // the rows of out among themselves: the axis with the smaller stride holds whole rows, the other whole runs of it (an axis of one index has no stride)
+    {
+        int64_t s1 = n_inner > 1 ? ld_oi : -1, n1 = n_inner, s2 = n_outer > 1 ? ld_oo : -1, n2 = n_outer;
+        if (s2 >= 0 && (s1 < 0 || s2 < s1)) { std::swap(s1, s2); std::swap(n1, n2); }
+        if ((s1 >= 0 && s1 < cols) || (s2 >= 0 && s2 < (n1 - 1) * s1 + cols))
+            return fail(PQ_ERR_BAD_ARG, "%s: the rows of out overlap each other (ld_oo=%lld ld_oi=%lld n_outer=%lld n_inner=%lld cols=%lld)", fn, (long long)ld_oo,
+                        (long long)ld_oi, (long long)n_outer, (long long)n_inner, (long long)cols);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::head_rmsnorm_dispatch<dt>(x, ld_xo, ld_xi, weight, eps, gain, n_outer, n_inner, cols, out, ld_oo, ld_oi, st); });
+    return check_launch(fn);
+}
+
 int32_t pq_scaled_add_rmsnorm_quant_rows(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, float multiplier, void* sum_out, int64_t ld_s, const void* weight,
                                          float eps, int32_t dtype, int64_t rows, int64_t cols, int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
     Range range_("pq:scaled_add_rmsnorm_quant (K1ma / K1mo)");

@@ -52,6 +52,9 @@ template <int DT> void gemma_postnorm_add_rmsnorm_quant_dispatch(const void* x, 
 // ---- olmo_postnorm_kernels.hip: the post-norm flow of OLMo-2 / OLMo-3 (K1oq; q == scale == nullptr: K1oa; res == nullptr as well: K1on, the norm alone)
 template <int DT> void olmo_postnorm_add_quant_dispatch(const void* x, int64_t ldx, const void* pwgt, float post_eps, const void* res, int64_t ldr, void* sum_out, int64_t lds,
                                                         int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, hipStream_t st);
+// ---- head_norm_kernels.hip: the per-head norm of q and k (K1hn; gain: PQ_GAIN_LLAMA / PQ_GAIN_GEMMA; operands addressed as base + o * ld_o + i * ld_i + c, in elements)
+template <int DT> void head_rmsnorm_dispatch(const void* x, int64_t ld_xo, int64_t ld_xi, const void* wgt, float eps, int gain, int64_t n_outer, int64_t n_inner, int64_t cols,
+                                             void* out, int64_t ld_oo, int64_t ld_oi, hipStream_t st);
 // ---- scaled_addnorm_kernels.hip: the scaled residual add of the Granite decoders (K1ma; wgt == nullptr: the add-only form K1mo — q, scale and h_out are null as well)
 template <int DT> void scaled_add_rmsnorm_quant_dispatch(const void* x, int64_t ldx, const void* res, int64_t ldr, float mult, void* sum_out, int64_t lds, const void* wgt,
                                                          float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);

@@ -18,7 +18,8 @@
 
 ``swap_linears(model)`` must have run first.  Nothing is recognised by class name: a norm is probed (``is_gemma_rmsnorm`` runs its class's forward against the
 formula), its use is probed (``gptlike.fusable_norms``), the activation is probed (``gptlike.activation_kind``), the MLP's forward is probed.  The embedding
-scaling, the attention softcapping, the sliding windows, ``q_norm`` / ``k_norm`` and the final norm stay the model's code."""
+scaling, the attention softcapping, the sliding windows, ``q_norm`` / ``k_norm`` and the final norm stay the model's code (Gemma-3's per-head ``q_norm`` / ``k_norm`` are taken by
+``qk_norm.fuse_qk_norms``, an entry of its own, called last)."""
 from __future__ import annotations
 
 import types

@@ -772,6 +772,85 @@ def olmo_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, out: 
     return h
 
 
+def _head_stride_order(shape, strides):
+    """the leading axes of a [..., D] tensor from the outermost to the innermost by stride (stable: equal strides keep their order)"""
+    return sorted(range(len(shape) - 1), key=lambda a: -strides[a])
+
+
+def _dense_head_strides(shape, strides):
+    """strides of a dense tensor of `shape` whose last axis is innermost and whose leading axes are laid out in the stride order of `strides`: what eager's
+    elementwise chain returns for such an input"""
+    out = [0] * len(shape)
+    out[-1] = 1
+    step = max(int(shape[-1]), 1)
+    for a in reversed(_head_stride_order(shape, strides)):
+        out[a] = step
+        step *= max(int(shape[a]), 1)
+    return tuple(out)
+
+
+def _collapse_heads(shape, strides):
+    """The leading axes of a [..., D] tensor as at most two strided axes: (n_outer, ld_o, n_inner, ld_i), in elements, or None where a copy is needed.  The axes are
+    ordered by stride and an axis is merged into its neighbour where stride[a] == stride[b] * size[b]; axes of one index are dropped.  q_proj(x).view(B, T, H, D) on a
+    column slice of a fused q/k/v output, its .transpose(1, 2) and a contiguous tensor all collapse (the last to ONE axis: (rows, D, 1, D)).  None: the last stride is
+    not 1, a stride is smaller than D (rows that overlap: an expanded axis), or more than two axes remain."""
+    D = int(shape[-1])
+    if D > 1 and strides[-1] != 1:
+        return None
+    groups = []          # (size, stride), outermost first
+    for a in _head_stride_order(shape, strides):
+        n, s = int(shape[a]), int(strides[a])
+        if n == 1:
+            continue
+        if s < D:
+            return None
+        if groups and groups[-1][1] == s * n:
+            groups[-1] = (groups[-1][0] * n, s)
+        else:
+            groups.append((n, s))
+    if len(groups) > 2:
+        return None
+    if not groups:
+        return (1, D, 1, D)
+    if len(groups) == 1:
+        return (groups[0][0], groups[0][1], 1, D)
+    return (groups[0][0], groups[0][1], groups[1][0], groups[1][1])
+
+
+def head_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, kind: str = "llama") -> torch.Tensor:
+    """The RMSNorm of every row of the LAST axis of x in ONE kernel (K1hn: q_norm / k_norm of Qwen3, Qwen3-MoE and Gemma-3, whose rows are heads of head_dim
+    elements), no quantisation.  kind "llama": (weight * (x.float() * rsqrt(mean(x.float()², -1) + eps)).to(x.dtype)) — x * rs rounded to the storage dtype before the
+    gain (QSPEC N1-N5; Qwen3RMSNorm, LlamaRMSNorm); kind "gemma": ((x.float() * rs) * (1 + weight.float())).to(x.dtype), one rounding (NG1-NG5; Gemma3RMSNorm).  The
+    bits are those of rmsnorm_quantize(..., return_h=True)[1] / gemma_rmsnorm_quantize(..., return_h=True)[1] on the same rows (QSPEC HN1): spec-exact, eager-close.
+    x: [..., D] on the GPU; weight: [D], the same dtype and device.  The leading axes are collapsed into at most two strided axes (_collapse_heads), so
+    q_proj(x).view(B, T, H, D) on a column slice of a fused q/k/v output, its .transpose(1, 2) and a contiguous tensor are normed where they lie, without a copy;
+    anything else is copied once.  Returns a fresh dense tensor of x's shape whose axes are laid out in x's stride order, as eager's elementwise chain does.  An
+    empty x returns an empty tensor without a launch."""
+    what = "head_rmsnorm"
+    L.require_gpu(x, f"{what}(x)")
+    L.require_gpu(weight, f"{what}(weight)")
+    _check_norm_weight(what, x, weight)
+    if kind not in L.GAIN_KINDS:
+        raise ValueError(f"{what}: kind must be one of {sorted(L.GAIN_KINDS)}, got {kind!r}")
+    code = L.dtype_code(x.dtype)
+    dense = _dense_head_strides(x.shape, x.stride())
+    out = torch.empty_strided(x.shape, dense, dtype=x.dtype, device=x.device)
+    if x.numel() == 0:
+        return out
+    plan = _collapse_heads(x.shape, x.stride())
+    if plan is None:          # one copy, into the layout of the result
+        xc = torch.empty_strided(x.shape, dense, dtype=x.dtype, device=x.device)
+        xc.copy_(x)
+        x, plan = xc, _collapse_heads(x.shape, dense)
+    n_outer, ld_xo, n_inner, ld_xi = plan
+    D = x.shape[-1]
+    w = weight.contiguous()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().pq_head_rmsnorm(x.data_ptr(), ld_xo, ld_xi, w.data_ptr(), float(eps), L.GAIN_KINDS[kind], code, n_outer, n_inner, D, out.data_ptr(),
+                                        n_inner * D, D, L.stream_ptr(x)), what)
+    return out
+
+
 def gelu_mul_quantize(g: torch.Tensor, u: torch.Tensor, kind: str = "gelu_tanh", return_h: bool = False):
     """quantize(F.gelu(g, approximate="tanh") * u, axis=-1) in ONE pass (kernel K1gg): the activation of the down projection of a GeGLU MLP (Gemma's
     down(act_fn(gate(x)) * up(x))) is computed, reduced and encoded in registers.  g and u may be the column halves of one fused gate+up output.  Numerics: QSPEC
