@@ -468,6 +468,28 @@ int32_t pq_moe_route(const void* topk_ids, int32_t ids_are_int64, int64_t ld_ids
 int32_t pq_moe_combine(const void* y, int64_t ldy, int32_t dtype, int64_t M_total, const int32_t* rows_of, const int32_t* slot_of,
                        const void* topk_w, int64_t ld_w, int64_t T, int32_t k, int64_t H, void* out, int64_t ld_out, void* stream);
 
+/* EXPERT SELECTION of a mixture-of-experts router behind its GEMM (moe_topk_kernels.hip, kernel K-rt; QSPEC RT1-RT5): from logits[T, E] the k experts of
+ * every token and their routing weights, in ONE launch, where model code runs softmax, topk, a sum, a division and a cast.
+ *   ids[t, 0 .. k-1]   the k largest logits of the row, slot 0 the largest (torch.topk(sorted=True)); NaN sorts above +Inf, -0 == +0, EQUAL VALUES GO TO THE LOWER EXPERT
+ *                      ID.  Always distinct and in [0, E), whatever the row holds.  The selection compares the logits, not the probabilities.
+ *   kind = PQ_ROUTER_SOFTMAX_TOPK (Mixtral, Qwen2-MoE, Qwen3-MoE, OLMoE):  m = l[ids[0]];  x[e] = exp_spec(l[e] - m) (QSPEC S1-S4);  S = the sum of x over the row in the
+ *                      pinned order of RT3 (it depends on E alone);  p[j] = x[ids[j]] / S;  with renormalise: s = ((p[0] + p[1]) + ...) in slot order, w[j] = p[j] / s,
+ *                      without it w[j] = p[j]
+ *   kind = PQ_ROUTER_TOPK_SOFTMAX (GPT-OSS):  x[j] = exp_spec(l[ids[j]] - m);  s = ((x[0] + x[1]) + ...);  w[j] = x[j] / s.  Only the k selected logits decide the
+ *                      weights; they sum to one by construction and `renormalise` changes nothing.
+ *   weights[t, j] = cast_rne(w[j]) to w_dtype; a NaN weight is the canonical quiet NaN.  Every division is an IEEE binary32 division.  A row whose maximum is NaN or
+ *   +-Inf gets NaN weights (inf - inf, as in eager) and the ids above.
+ *  - logits: `dtype` (bf16 / fp16 / f32), row stride ld_logits >= E elements; weights: w_dtype (any of the three, independent of `dtype`), row stride ld_w >= k; ids:
+ *    int32 (ids_are_int64 = 0) or int64 (1), row stride ld_ids >= k.  Each operand aligned to its element size; the outputs overlap neither each other nor the logits.
+ *    The logits are not written.
+ *  - 1 <= E <= 1024, 1 <= k <= min(E, 64), T >= 0, T < 2^31.  T == 0 is a no-op.  renormalise: 0 or 1.
+ *  - no atomics, no LDS, no workspace, no wait on another workgroup, no host read: capturable into a hipGraph, and a replay is right when only the CONTENTS of the
+ *    logits changed.  The bits do not depend on T, on the leading dimensions or on which tokens share a wave. */
+#define PQ_ROUTER_SOFTMAX_TOPK 0
+#define PQ_ROUTER_TOPK_SOFTMAX 1
+int32_t pq_moe_topk(const void* logits, int32_t dtype, int64_t ld_logits, int64_t T, int32_t E, int32_t k, int32_t kind, int32_t renormalise,
+                    void* weights, int32_t w_dtype, int64_t ld_w, void* ids, int32_t ids_are_int64, int64_t ld_ids, void* stream);
+
 /* qlinear.forward in ONE call: y[M,N] = qlinear(x[M,K]) with dynamic per-token quantisation of x (K1), the int8 MFMA GEMM
  * and the fused dequant epilogue, output dtype = input dtype.  Scratch (xq, xs, optional split-K slabs) is carved from
  * `workspace` (>= pq_qlinear_dyn_workspace_bytes(M,N,K), 256-byte aligned, caller-owned, reusable across calls on one

@@ -16,6 +16,7 @@ PQ_BF16, PQ_FP16, PQ_F32 = 0, 1, 2
 GLU_KINDS = {"clamped_silu": 0, "alpha_sigmoid": 1}        # PQ_GLU_* of include/pq_hip.h
 ACT_KINDS = {"relu": 0, "gelu_tanh": 1, "gelu_erf": 2}     # PQ_ACT_* of include/pq_hip.h
 GAIN_KINDS = {"llama": 0, "gemma": 1}                      # PQ_GAIN_* of include/pq_hip.h
+ROUTER_KINDS = {"softmax_topk": 0, "topk_softmax": 1}      # PQ_ROUTER_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
 EXPORTS = (
@@ -37,6 +38,7 @@ EXPORTS = (
     "pq_olmo_postnorm_add_quant_rowwise",
     "pq_scaled_add_rmsnorm_quant_rows",
     "pq_head_rmsnorm",
+    "pq_moe_topk",
 )
 
 _lib = None
@@ -115,6 +117,8 @@ def lib() -> ctypes.CDLL:
     L.pq_moe_route.argtypes = [vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.pq_moe_combine.restype = i32
     L.pq_moe_combine.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, i64, vp, i64, vp]
+    L.pq_moe_topk.restype = i32
+    L.pq_moe_topk.argtypes = [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]
     L.pq_silu_mul_quant_rowwise.restype = i32
     L.pq_silu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp, i64, vp]
     L.pq_glu_quant_rowwise.restype = i32

@@ -1135,6 +1135,37 @@ int32_t pq_moe_combine(const void* y, int64_t ldy, int32_t dtype, int64_t M_tota
     return check_launch(what);
 }
 
+int32_t pq_moe_topk(const void* logits, int32_t dtype, int64_t ld_logits, int64_t T, int32_t E, int32_t k, int32_t kind, int32_t renormalise, void* weights, int32_t w_dtype,
+                    int64_t ld_w, void* ids, int32_t ids_are_int64, int64_t ld_ids, void* stream) {
+    Range range_("pq:moe_topk (K-rt)");
+    const char* what = "pq_moe_topk";
+    if (const int32_t rc = check_dtype(what, dtype)) return rc;
+    if (w_dtype < 0 || w_dtype > 2) return fail(PQ_ERR_BAD_ARG, "%s: unknown w_dtype %d", what, w_dtype);
+    if (kind != PQ_ROUTER_SOFTMAX_TOPK && kind != PQ_ROUTER_TOPK_SOFTMAX)
+        return fail(PQ_ERR_BAD_ARG, "%s: unknown kind %d (0 = softmax_topk, 1 = topk_softmax)", what, kind);
+    if (renormalise != 0 && renormalise != 1) return fail(PQ_ERR_BAD_ARG, "%s: renormalise = %d (0 or 1)", what, renormalise);
+    if (ids_are_int64 != 0 && ids_are_int64 != 1) return fail(PQ_ERR_BAD_ARG, "%s: ids_are_int64 = %d (0 = int32 ids, 1 = int64 ids)", what, ids_are_int64);
+    if (const int32_t st = moe_dims_check(what, T, k, E, true)) return st;
+    if (k > E) return fail(PQ_ERR_BAD_ARG, "%s: k = %d > E = %d", what, k, E);
+    if (ld_logits < E) return fail(PQ_ERR_BAD_ARG, "%s: ld_logits = %lld < E = %d", what, (long long)ld_logits, E);
+    if (ld_w < k) return fail(PQ_ERR_BAD_ARG, "%s: ld_w = %lld < k = %d", what, (long long)ld_w, k);
+    if (ld_ids < k) return fail(PQ_ERR_BAD_ARG, "%s: ld_ids = %lld < k = %d", what, (long long)ld_ids, k);
+    if (T == 0) return PQ_OK;
+    if (!logits || !weights || !ids) return fail(PQ_ERR_BAD_ARG, "%s: %s is null", what, !logits ? "logits" : (!weights ? "weights" : "ids"));
+    const int64_t eb = dtype_bytes(dtype), wb = dtype_bytes(w_dtype), ib = ids_are_int64 ? 8 : 4;
+    if ((reinterpret_cast<uintptr_t>(logits) & (uintptr_t)(eb - 1)) != 0) return fail(PQ_ERR_BAD_ALIGN, "%s: logits is not aligned to its element size", what);
+    if ((reinterpret_cast<uintptr_t>(weights) & (uintptr_t)(wb - 1)) != 0) return fail(PQ_ERR_BAD_ALIGN, "%s: weights is not aligned to its element size", what);
+    if ((reinterpret_cast<uintptr_t>(ids) & (uintptr_t)(ib - 1)) != 0) return fail(PQ_ERR_BAD_ALIGN, "%s: ids is not aligned to its element size", what);
+    {
+        const NamedExtent ops[] = {{"logits", extent_of(logits, ld_logits, T, E, eb), false}, {"weights", extent_of(weights, ld_w, T, k, wb), true},
+                                   {"ids", extent_of(ids, ld_ids, T, k, ib), true}};
+        if (const int32_t rc = check_disjoint(what, ops, 3)) return rc;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(dtype, [&](auto dt) { pq::moe_topk_dispatch<dt>(logits, ld_logits, T, E, k, kind, renormalise, weights, w_dtype, ld_w, ids, ids_are_int64 != 0, ld_ids, st); });
+    return check_launch(what);
+}
+
 // ---- one-call dynamic qlinear: K1 (x -> xq, xs in the workspace) then pq_qlinear_s8 (with split-K slabs if planned).
 
 size_t pq_qlinear_dyn_workspace_bytes(int64_t M, int64_t N, int64_t K) {

@@ -92,4 +92,7 @@ void launch_moe_route(const void* ids, bool ids_are_int64, int64_t ld_ids, int64
                       const float* xs, float* xs_sorted, void* workspace, hipStream_t st);
 template <int DT> void moe_combine_dispatch(const void* y, int64_t ldy, int64_t M_total, const int32_t* rows_of, const int32_t* slot_of, const void* w, int64_t ld_w, int64_t T,
                                             int k, int64_t H, void* out, int64_t ld_out, hipStream_t st);
+// ---- moe_topk_kernels.hip: the expert selection behind the router GEMM (K-rt; DT: the logits' dtype; kind: PQ_ROUTER_*; w_dtype: a PQ_* dtype code of its own)
+template <int DT> void moe_topk_dispatch(const void* logits, int64_t ld_logits, int64_t T, int E, int k, int kind, int renormalise, void* weights, int w_dtype, int64_t ld_w,
+                                         void* ids, bool ids_are_int64, int64_t ld_ids, hipStream_t st);
 }  // namespace pq

@@ -15,7 +15,9 @@ swap_moe_experts replaces the routed experts of a decoder's sparse MoE blocks, i
 
 route_plan and combine are the same two steps as pure tensor code that runs on any device: the DEFINITION moe_route and moe_combine are held to, element for element and
 bit for bit (tests/test_gpu_moe_route.py, tests/test_gpu_moe_combine.py), and what MoEGatedMLP runs with torch_plumbing = True (A/B: tools/moe_layer_bench.py).  The expert
-SELECTION — router GEMM, softmax, top-k, renormalisation — stays the model's torch code: its bits decide which expert a token goes to.
+SELECTION — router GEMM, softmax, top-k, renormalisation — stays the model's torch code by default: its bits decide which expert a token goes to.  moe_topk (C-ABI
+pq_moe_topk, kernel K-rt) is everything behind the router GEMM in one launch, to a specification of its own (QSPEC RT); fuse_moe_routers (moe_router.py) and
+MoEBlock.hip_routing switch it on.
 Nothing here reads a routing result on the host: the forward is capturable into a hipGraph and replayable for other routings."""
 from __future__ import annotations
 
@@ -202,6 +204,34 @@ def moe_combine(y: torch.Tensor, rows_of: torch.Tensor, slot_of: torch.Tensor, t
     return out
 
 
+def moe_topk(logits: torch.Tensor, top_k: int, kind: str = "softmax_topk", renormalise: bool = False, out_dtype: torch.dtype | None = None,
+             ids_dtype: torch.dtype = torch.int64):
+    """The expert selection behind a router's GEMM as ONE launch of the library (C-ABI pq_moe_topk, kernel K-rt; QSPEC RT1-RT5): logits [..., E] bf16 / fp16 / f32 on the
+    GPU (leading axes collapsed to rows; a view whose last axis is not contiguous is copied once) -> (weights [..., top_k] in out_dtype — default: the logits' dtype —,
+    ids [..., top_k] int64 or int32, slot 0 the largest logit, equal logits to the lower expert id).
+    kind "softmax_topk": softmax over all experts, the k largest, with renormalise divided by their sum (Mixtral, Qwen-MoE, OLMoE); "topk_softmax": the k largest logits,
+    softmax over those (GPT-OSS; renormalise changes nothing).  The softmax is the specified one (exp_spec, a pinned summation order), not the vendor's."""
+    if kind not in L.ROUTER_KINDS:
+        raise ValueError(f"moe_topk: unknown kind {kind!r}, expected one of {tuple(L.ROUTER_KINDS)}")
+    L.require_gpu(logits, "moe_topk(logits)")
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"moe_topk: ids_dtype must be torch.int32 or torch.int64, got {ids_dtype}")
+    if logits.dim() < 1:
+        raise ValueError("moe_topk: logits must have at least one axis")
+    code = L.dtype_code(logits.dtype)
+    w_dtype = logits.dtype if out_dtype is None else out_dtype
+    w_code = L.dtype_code(w_dtype)
+    lead, E = tuple(logits.shape[:-1]), logits.shape[-1]
+    x2 = L.row_major_2d(logits if logits.dim() == 2 else logits.reshape(-1, E))
+    T, k, dev = x2.shape[0], int(top_k), logits.device
+    weights = torch.empty((T, max(k, 0)), dtype=w_dtype, device=dev)
+    ids = torch.empty((T, max(k, 0)), dtype=ids_dtype, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().pq_moe_topk(x2.data_ptr(), code, L.ld(x2), T, E, k, L.ROUTER_KINDS[kind], 1 if renormalise else 0, weights.data_ptr(), w_code, max(k, 1),
+                                    ids.data_ptr(), 1 if ids_dtype == torch.int64 else 0, max(k, 1), L.stream_ptr(x2)), "moe_topk")
+    return weights.reshape(lead + (k,)), ids.reshape(lead + (k,))
+
+
 GATE_KINDS = ("silu", "clamped_silu", "alpha_sigmoid")
 
 
@@ -309,7 +339,11 @@ class MoEGatedMLP(nn.Module):
 
 class MoEBlock(nn.Module):
     """What swap_moe_experts puts in place of a sparse MoE block: the block's own router (`gate`) and routing recipe — softmax over the experts in f32, top-k,
-    optional renormalisation, weights cast to the hidden dtype — in front of MoEGatedMLP."""
+    optional renormalisation, weights cast to the hidden dtype — in front of MoEGatedMLP.
+    hip_routing = True (set per instance by fuse_moe_routers) runs that recipe as ONE moe_topk launch whose int32 ids go straight into moe_route; the softmax is then the
+    specified one (QSPEC RT3), close to eager's but not its bits."""
+
+    hip_routing = False
 
     def __init__(self, gate: nn.Module, experts: MoEGatedMLP, top_k: int, renormalise: bool, return_router_logits: bool):
         super().__init__()
@@ -319,6 +353,10 @@ class MoEBlock(nn.Module):
     def forward(self, hidden_states: torch.Tensor):
         x2 = hidden_states.reshape(-1, hidden_states.shape[-1])
         router_logits = self.gate(x2)
+        if self.hip_routing:
+            weights, selected = moe_topk(router_logits, self.top_k, "softmax_topk", self.renormalise, out_dtype=hidden_states.dtype, ids_dtype=torch.int32)
+            out = self.experts(x2, selected, weights).reshape(hidden_states.shape)
+            return (out, router_logits) if self.return_router_logits else out
         weights = torch.softmax(router_logits, dim=1, dtype=torch.float)
         weights, selected = torch.topk(weights, self.top_k, dim=-1)
         if self.renormalise:
