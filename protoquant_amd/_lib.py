@@ -19,30 +19,75 @@ GAIN_KINDS = {"llama": 0, "gemma": 1}                      # PQ_GAIN_* of includ
 ROUTER_KINDS = {"softmax_topk": 0, "topk_softmax": 1}      # PQ_ROUTER_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
-EXPORTS = (
-    "pq_version", "pq_last_error", "pq_quant_rowwise", "pq_quant_colwise", "pq_dequant",
-    "pq_gemm_s8s8s32", "pq_qlinear_s8", "pq_qlinear_workspace_bytes", "pq_gemm_variant_name",
-    "pq_selftest_fast_quotient", "pq_selftest_half_encode", "pq_selftest_silu_short", "pq_qlinear_dyn", "pq_qlinear_dyn_workspace_bytes", "pq_silu_mul_quant_rowwise",
-    "pq_rmsnorm_quant_rowwise", "pq_set_option", "pq_qlinear_s8_t", "pq_qlinear_t_workspace_bytes",
-    "pq_silu_mul_rowamax", "pq_silu_mul_quant_rowwise_amax", "pq_qlinear_s8_kslabs", "pq_qlinear_kslabs_workspace_bytes", "pq_qlinear_kslabs_workspace_bytes_for", "pq_kslabs_way_name",
-    "pq_quant_rowamax", "pq_quant_rowwise_amax",
-    "pq_qlinear_s8_grouped", "pq_gemm_s8s8s32_grouped", "pq_grouped_variant_name",
-    "pq_qlinear_s8_grouped_stream", "pq_gemm_s8s8s32_grouped_stream", "pq_grouped_stream_plan_name",
-    "pq_moe_route", "pq_moe_route_workspace_bytes", "pq_moe_combine",
-    "pq_glu_quant_rowwise", "pq_selftest_glu_short",
-    "pq_add_rmsnorm_quant_rowwise",
-    "pq_layernorm_quant_rowwise", "pq_act_quant_rowwise",
-    "pq_add_layernorm_quant_rowwise", "pq_parallel_layernorm_quant_rowwise",
-    "pq_gemma_rmsnorm_quant_rowwise", "pq_add_gemma_rmsnorm_quant_rowwise", "pq_gelu_mul_quant_rowwise",
-    "pq_gemma_postnorm_add_rmsnorm_quant_rowwise",
-    "pq_olmo_postnorm_add_quant_rowwise",
-    "pq_scaled_add_rmsnorm_quant_rows",
-    "pq_head_rmsnorm",
-    "pq_moe_topk",
-)
-
 _lib = None
-i32, i64, vp, sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
+i32, i64, vp, sz, f32, cstr = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_char_p
+
+# symbol -> (restype, argtypes), the prototypes of include/pq_hip.h (tests/test_abi.py compares the two, parameter by parameter); None: no parameters.  Entries that
+# share a prototype share its list.
+_QUANT = [vp, i32, i64, i64, i64, vp, i64, vp, vp]
+_QLINEAR = [vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]
+_WORKSPACE = [i64, i64, i64]
+_GROUPED = [vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, i32, i64, i64, i64, vp, i64, i32, vp]
+_GROUPED_GEMM = [vp, i64, vp, i64, vp, i64, i64, vp, i32, i64, i64, i64, vp, i64, vp]
+_GROUPED_NAME = [i32, i64, i64, i64]
+_RMSNORM = [vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+_ADD_RMSNORM = [vp, i64, vp, i64, vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]
+_SELFTEST = [i32, vp, vp]
+SIGNATURES = {
+    "pq_version": (i32, None),
+    "pq_last_error": (cstr, None),
+    "pq_quant_rowwise": (i32, _QUANT),
+    "pq_quant_colwise": (i32, _QUANT),
+    "pq_dequant": (i32, [vp, i64, vp, i32, i64, i64, vp, i64, i32, vp]),
+    "pq_gemm_s8s8s32": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp]),
+    "pq_qlinear_s8": (i32, _QLINEAR),
+    "pq_qlinear_workspace_bytes": (sz, _WORKSPACE),
+    "pq_gemm_variant_name": (cstr, [i64, i64, i64, i64, i64]),
+    "pq_selftest_fast_quotient": (i32, [vp, vp, i64, vp, vp]),
+    "pq_selftest_half_encode": (i32, _SELFTEST),
+    "pq_selftest_silu_short": (i32, _SELFTEST),
+    "pq_qlinear_dyn": (i32, [vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp, sz, vp]),
+    "pq_qlinear_dyn_workspace_bytes": (sz, _WORKSPACE),
+    "pq_silu_mul_quant_rowwise": (i32, [vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_rmsnorm_quant_rowwise": (i32, _RMSNORM),
+    "pq_set_option": (i32, [cstr, cstr]),
+    "pq_qlinear_s8_t": (i32, _QLINEAR),
+    "pq_qlinear_t_workspace_bytes": (sz, _WORKSPACE),
+    "pq_silu_mul_rowamax": (i32, [vp, i64, vp, i64, i32, i64, i64, vp, vp]),
+    "pq_silu_mul_quant_rowwise_amax": (i32, [vp, i64, vp, i64, i32, i64, i64, vp, vp, i64, vp, vp]),
+    "pq_qlinear_s8_kslabs": (i32, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]),
+    "pq_qlinear_kslabs_workspace_bytes": (sz, [i64, i64, i64, i64]),
+    "pq_qlinear_kslabs_workspace_bytes_for": (sz, [vp, i64, i64, i64, vp, i64, i64, i64, i64]),
+    "pq_kslabs_way_name": (cstr, [vp, i64, i64, i64, vp, i64, i64, i64, i64, sz]),
+    "pq_quant_rowamax": (i32, [vp, i32, i64, i64, i64, vp, vp]),
+    "pq_quant_rowwise_amax": (i32, [vp, i32, i64, i64, i64, vp, vp, i64, vp, vp]),
+    "pq_qlinear_s8_grouped": (i32, _GROUPED),
+    "pq_gemm_s8s8s32_grouped": (i32, _GROUPED_GEMM),
+    "pq_grouped_variant_name": (cstr, _GROUPED_NAME),
+    "pq_qlinear_s8_grouped_stream": (i32, _GROUPED),
+    "pq_gemm_s8s8s32_grouped_stream": (i32, _GROUPED_GEMM),
+    "pq_grouped_stream_plan_name": (cstr, _GROUPED_NAME),
+    "pq_moe_route": (i32, [vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "pq_moe_route_workspace_bytes": (sz, [i64, i32, i32]),
+    "pq_moe_combine": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, i64, vp, i64, vp]),
+    "pq_glu_quant_rowwise": (i32, [vp, i64, vp, i64, i32, i64, i64, i32, f32, f32, vp, i64, vp, vp, i64, vp]),
+    "pq_selftest_glu_short": (i32, [i32, i32, f32, f32, vp, vp]),
+    "pq_add_rmsnorm_quant_rowwise": (i32, _ADD_RMSNORM),
+    "pq_layernorm_quant_rowwise": (i32, [vp, i64, vp, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_act_quant_rowwise": (i32, [vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]),
+    "pq_add_layernorm_quant_rowwise": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_parallel_layernorm_quant_rowwise": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, f32, vp, vp, f32, i32, i64, i64,
+                                                  vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_gemma_rmsnorm_quant_rowwise": (i32, _RMSNORM),
+    "pq_add_gemma_rmsnorm_quant_rowwise": (i32, _ADD_RMSNORM),
+    "pq_gelu_mul_quant_rowwise": (i32, [vp, i64, vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]),
+    "pq_gemma_postnorm_add_rmsnorm_quant_rowwise": (i32, [vp, i64, vp, f32, vp, i64, vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_olmo_postnorm_add_quant_rowwise": (i32, [vp, i64, vp, f32, vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp]),
+    "pq_scaled_add_rmsnorm_quant_rows": (i32, [vp, i64, vp, i64, f32, vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
+    "pq_head_rmsnorm": (i32, [vp, i64, i64, vp, f32, i32, i32, i64, i64, i64, vp, i64, i64, vp]),
+    "pq_moe_topk": (i32, [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 class PQError(RuntimeError):
@@ -59,107 +104,11 @@ def lib() -> ctypes.CDLL:
         raise PQError(f"{LIB_PATH} not found: build it with `make -C protoquant_amd/csrc` "
                       "(protoquant_amd has no CPU/eager fallback)")
     L = ctypes.CDLL(LIB_PATH)
-    L.pq_version.restype = i32
-    L.pq_last_error.restype = ctypes.c_char_p
-    L.pq_gemm_variant_name.restype = ctypes.c_char_p
-    L.pq_gemm_variant_name.argtypes = [i64, i64, i64, i64, i64]
-    L.pq_qlinear_workspace_bytes.restype = sz
-    L.pq_qlinear_workspace_bytes.argtypes = [i64, i64, i64]
-    L.pq_quant_rowwise.restype = i32
-    L.pq_quant_rowwise.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, vp]
-    L.pq_quant_colwise.restype = i32
-    L.pq_quant_colwise.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, vp]
-    L.pq_dequant.restype = i32
-    L.pq_dequant.argtypes = [vp, i64, vp, i32, i64, i64, vp, i64, i32, vp]
-    L.pq_gemm_s8s8s32.restype = i32
-    L.pq_gemm_s8s8s32.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp]
-    L.pq_qlinear_s8.restype = i32
-    L.pq_qlinear_s8.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]
-    L.pq_qlinear_s8_t.restype = i32
-    L.pq_qlinear_s8_t.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]
-    L.pq_qlinear_t_workspace_bytes.restype = sz
-    L.pq_qlinear_t_workspace_bytes.argtypes = [i64, i64, i64]
-    L.pq_qlinear_dyn_workspace_bytes.restype = sz
-    L.pq_qlinear_dyn_workspace_bytes.argtypes = [i64, i64, i64]
-    L.pq_qlinear_dyn.restype = i32
-    L.pq_qlinear_dyn.argtypes = [vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp, sz, vp]
-    L.pq_silu_mul_rowamax.restype = i32
-    L.pq_silu_mul_rowamax.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, vp]
-    L.pq_silu_mul_quant_rowwise_amax.restype = i32
-    L.pq_silu_mul_quant_rowwise_amax.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, vp, i64, vp, vp]
-    L.pq_quant_rowamax.restype = i32
-    L.pq_quant_rowamax.argtypes = [vp, i32, i64, i64, i64, vp, vp]
-    L.pq_quant_rowwise_amax.restype = i32
-    L.pq_quant_rowwise_amax.argtypes = [vp, i32, i64, i64, i64, vp, vp, i64, vp, vp]
-    L.pq_qlinear_kslabs_workspace_bytes.restype = sz
-    L.pq_qlinear_kslabs_workspace_bytes.argtypes = [i64, i64, i64, i64]
-    L.pq_qlinear_kslabs_workspace_bytes_for.restype = sz
-    L.pq_qlinear_kslabs_workspace_bytes_for.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i64]
-    L.pq_kslabs_way_name.restype = ctypes.c_char_p
-    L.pq_kslabs_way_name.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i64, sz]
-    L.pq_qlinear_s8_kslabs.restype = i32
-    L.pq_qlinear_s8_kslabs.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i64, i64, i64, vp, sz, vp]
-    L.pq_qlinear_s8_grouped.restype = i32
-    L.pq_qlinear_s8_grouped.argtypes = [vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, i32, i64, i64, i64, vp, i64, i32, vp]
-    L.pq_gemm_s8s8s32_grouped.restype = i32
-    L.pq_gemm_s8s8s32_grouped.argtypes = [vp, i64, vp, i64, vp, i64, i64, vp, i32, i64, i64, i64, vp, i64, vp]
-    L.pq_grouped_variant_name.restype = ctypes.c_char_p
-    L.pq_grouped_variant_name.argtypes = [i32, i64, i64, i64]
-    L.pq_qlinear_s8_grouped_stream.restype = i32
-    L.pq_qlinear_s8_grouped_stream.argtypes = L.pq_qlinear_s8_grouped.argtypes
-    L.pq_gemm_s8s8s32_grouped_stream.restype = i32
-    L.pq_gemm_s8s8s32_grouped_stream.argtypes = L.pq_gemm_s8s8s32_grouped.argtypes
-    L.pq_grouped_stream_plan_name.restype = ctypes.c_char_p
-    L.pq_grouped_stream_plan_name.argtypes = [i32, i64, i64, i64]
-    L.pq_moe_route_workspace_bytes.restype = sz
-    L.pq_moe_route_workspace_bytes.argtypes = [i64, i32, i32]
-    L.pq_moe_route.restype = i32
-    L.pq_moe_route.argtypes = [vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.pq_moe_combine.restype = i32
-    L.pq_moe_combine.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, i64, vp, i64, vp]
-    L.pq_moe_topk.restype = i32
-    L.pq_moe_topk.argtypes = [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]
-    L.pq_silu_mul_quant_rowwise.restype = i32
-    L.pq_silu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_glu_quant_rowwise.restype = i32
-    L.pq_glu_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, i32, ctypes.c_float, ctypes.c_float, vp, i64, vp, vp, i64, vp]
-    L.pq_selftest_glu_short.restype = i32
-    L.pq_selftest_glu_short.argtypes = [i32, i32, ctypes.c_float, ctypes.c_float, vp, vp]
-    L.pq_rmsnorm_quant_rowwise.restype = i32
-    L.pq_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_add_rmsnorm_quant_rowwise.restype = i32
-    L.pq_add_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_layernorm_quant_rowwise.restype = i32
-    L.pq_layernorm_quant_rowwise.argtypes = [vp, i64, vp, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_add_layernorm_quant_rowwise.restype = i32
-    L.pq_add_layernorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_parallel_layernorm_quant_rowwise.restype = i32
-    L.pq_parallel_layernorm_quant_rowwise.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, ctypes.c_float, vp, vp, ctypes.c_float, i32, i64, i64,
-                                                      vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_act_quant_rowwise.restype = i32
-    L.pq_act_quant_rowwise.argtypes = [vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
-    L.pq_gemma_rmsnorm_quant_rowwise.restype = i32
-    L.pq_gemma_rmsnorm_quant_rowwise.argtypes = L.pq_rmsnorm_quant_rowwise.argtypes
-    L.pq_add_gemma_rmsnorm_quant_rowwise.restype = i32
-    L.pq_add_gemma_rmsnorm_quant_rowwise.argtypes = L.pq_add_rmsnorm_quant_rowwise.argtypes
-    L.pq_gemma_postnorm_add_rmsnorm_quant_rowwise.restype = i32
-    L.pq_gemma_postnorm_add_rmsnorm_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, vp, i64, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_olmo_postnorm_add_quant_rowwise.restype = i32
-    L.pq_olmo_postnorm_add_quant_rowwise.argtypes = [vp, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp]
-    L.pq_scaled_add_rmsnorm_quant_rows.restype = i32
-    L.pq_scaled_add_rmsnorm_quant_rows.argtypes = [vp, i64, vp, i64, ctypes.c_float, vp, i64, vp, ctypes.c_float, i32, i64, i64, vp, i64, vp, vp, i64, vp]
-    L.pq_head_rmsnorm.restype = i32
-    L.pq_head_rmsnorm.argtypes = [vp, i64, i64, vp, ctypes.c_float, i32, i32, i64, i64, i64, vp, i64, i64, vp]
-    L.pq_gelu_mul_quant_rowwise.restype = i32
-    L.pq_gelu_mul_quant_rowwise.argtypes = [vp, i64, vp, i64, i32, i64, i64, i32, vp, i64, vp, vp, i64, vp]
-    L.pq_set_option.restype = i32
-    L.pq_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-    L.pq_selftest_fast_quotient.restype = i32
-    L.pq_selftest_fast_quotient.argtypes = [vp, vp, i64, vp, vp]
-    L.pq_selftest_half_encode.restype = i32
-    L.pq_selftest_half_encode.argtypes = [i32, vp, vp]
-    L.pq_selftest_silu_short.restype = i32
-    L.pq_selftest_silu_short.argtypes = [i32, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     if L.pq_version() != ABI_VERSION:
         raise PQError(f"libpq_hip.so ABI {L.pq_version()} != expected {ABI_VERSION}")
     _lib = L

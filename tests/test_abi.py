@@ -42,6 +42,43 @@ def test_library_exports_every_declared_symbol():
     assert L.pq_gemm_variant_name(5, 7, 3, 3, 3) == b"generic64"
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter types]) of every prototype in include/pq_hip.h, as ctypes types: any T* is c_void_p except const char*"""
+    src = open(os.path.join(ROOT, "include", "pq_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    scalar = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
+
+    def ctype(decl, is_param):
+        words = decl.replace("*", " * ").split()
+        if is_param and words[-1] != "*":
+            words = words[:-1]                                            # the parameter's name
+        if words[-1] == "*":
+            return ctypes.c_char_p if words[:-1] == ["const", "char"] else ctypes.c_void_p
+        assert len(words) == 1, decl
+        return scalar[words[0]]
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(pq_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        params = params.strip()
+        protos[name] = (ctype(ret, False), None if params == "void" else [ctype(p, True) for p in params.split(",")])
+    return protos
+
+
+def test_bound_signatures_are_the_headers():
+    """restype and argtypes of every bound function against its prototype, parameter by parameter: a float bound as an int64, or two swapped arguments, would corrupt a
+    call silently"""
+    from protoquant_amd import _lib
+    L = _lib.lib()
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_lib.EXPORTS)
+    for name, (ret, params) in protos.items():
+        fn = getattr(L, name)
+        assert fn.restype is ret, (name, fn.restype, ret)
+        if params is not None:
+            assert fn.argtypes is not None and list(fn.argtypes) == params, (name, fn.argtypes, params)
+
+
 def test_rccl_library_exports_every_declared_symbol():
     src = open(os.path.join(ROOT, "include", "pq_rccl.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
