@@ -286,6 +286,22 @@ int32_t pq_scaled_add_rmsnorm_quant_rows(const void* x, int64_t ld_x, const void
 int32_t pq_head_rmsnorm(const void* x, int64_t ld_xo, int64_t ld_xi, const void* weight, float eps, int32_t gain, int32_t dtype, int64_t n_outer, int64_t n_inner,
                         int64_t cols, void* out, int64_t ld_oo, int64_t ld_oi, void* stream);
 
+/* K1h — a block-diagonal normalised Hadamard rotation of every row fused with K1 (hadamard_kernels.hip; QSPEC H1-H5): x W^T = (x R)(W R)^T for an
+ * orthogonal R, and with R = diag(H_B, .., H_B) / sqrt(B) an outlier channel is spread over its block of B elements before the per-token quantiser sees the row.
+ * x: [rows, cols] of `dtype` with leading dimension ld_x (elements); block: B, a power of two, 2 .. 4096, that divides cols.  Every block of B consecutive elements of a row
+ * is transformed on its own: v = f32(x); log2 B stages in ASCENDING stride, stage s turning every pair (i, i + 2^s) with bit s of i clear into (a + b, a - b), one binary32
+ * operation each; y = v * c with c the binary32 nearest to B^(-1/2); h = cast_rne(y) to `dtype`; then Q1-Q6 on the rows of h AS STORED: q [rows, cols] int8 with ld_q,
+ * scale [rows].  h_out (nullable, ld_h): also store h.  The outputs are those of pq_quant_rowwise run on h_out, bit for bit; a NaN anywhere in a block makes that block of
+ * h NaN (and the row's scale the canonical NaN, its codes 0), +Inf and -Inf in one block give NaN.
+ * q == scale == NULL is the transform-only form (the rotation of a weight: f32 in, f32 out): h_out is then required.  One of q / scale null without the other is
+ * PQ_ERR_BAD_ARG naming the missing argument.  No workspace, no atomics, one launch, graph-capturable.  Blocks of 64 .. 4096 on 16-byte aligned operands with rows of at
+ * most 32 768 elements run the register layouts; everything else a generic kernel with the same bits.
+ * q, scale and h_out may overlap neither x nor each other.  An unknown dtype, a block that is no power of two in 2 .. 4096 or does not divide cols, a null x, negative
+ * sizes, rows >= 2^31 and ld < cols are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.  rows == 0 or cols == 0: nothing is read or written,
+ * returns PQ_OK. */
+int32_t pq_hadamard_quant_rows(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld_x, int32_t block, int8_t* q, int64_t ld_q, float* scale, void* h_out,
+                               int64_t ld_h, void* stream);
+
 /* K1gg— K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6

@@ -85,6 +85,7 @@ SIGNATURES = {
     "pq_olmo_postnorm_add_quant_rowwise": (i32, [vp, i64, vp, f32, vp, i64, vp, i64, i32, i64, i64, vp, i64, vp, vp]),
     "pq_scaled_add_rmsnorm_quant_rows": (i32, [vp, i64, vp, i64, f32, vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
     "pq_head_rmsnorm": (i32, [vp, i64, i64, vp, f32, i32, i32, i64, i64, i64, vp, i64, i64, vp]),
+    "pq_hadamard_quant_rows": (i32, [vp, i32, i64, i64, i64, i32, vp, i64, vp, vp, i64, vp]),
     "pq_moe_topk": (i32, [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]),
 }
 EXPORTS = tuple(SIGNATURES)

@@ -60,6 +60,10 @@ template <int DT> void scaled_add_rmsnorm_quant_dispatch(const void* x, int64_t 
                                                          float eps, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
 template <int DT> void gelu_mul_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, int8_t* q, int64_t ldq, float* scale,
                                                void* h_out, int64_t ldh, hipStream_t st);
+// ---- hadamard_kernels.hip: the block Hadamard rotation fused with K1 (K1h; q == scale == nullptr: the transform alone, h_out required).  The error is that of the one
+// host call in front of the launch (the LDS size of a row of more than 12 288 elements), hipSuccess otherwise
+template <int DT> hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int64_t cols, int block, int8_t* q, int64_t ldq, float* scale, void* h_out,
+                                                     int64_t ldh, hipStream_t st);
 
 // ---- the GEMMs (K3 + K4): gemm_s8_generic.hip, gemm_s8_skinny.hip, gemm_s8_ring.hip, gemm_s8_fast.hip
 template <int OUT> void launch_gemm_generic(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb, const EpiArgs& epi, int64_t M, int64_t N, int64_t K, hipStream_t st);

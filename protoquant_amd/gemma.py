@@ -29,7 +29,7 @@ from torch import nn
 
 from .gptlike import activation_kind, fusable_norms
 from .llama import RMSNormQuant, _FusedSlice, _fuse_residual, fuse_llama_layers
-from .qlinear import FusedQLinear, GatedMLP, qlinear
+from .qlinear import FusedQLinear, GatedMLP, is_code_fed, qlinear
 from .qtensor import add_gemma_rmsnorm_quantize, gemma_postnorm_add, gemma_postnorm_add_rmsnorm_quantize, gemma_rmsnorm_quantize
 from .residual_flow import NamedFusedLayer, _forward_extra_params, _hooked, _ProbeLayer, attention, fuse_stacks, probe_named_flow
 
@@ -149,7 +149,7 @@ def _as_geglu(mlp: nn.Module):
     """GatedMLP(act="gelu_tanh") for a module whose gate_proj / up_proj / down_proj are qlinear, whose act_fn is the tanh GELU and whose forward is the gated
     flow; None for anything else"""
     g, u, d = (getattr(mlp, n, None) for n in ("gate_proj", "up_proj", "down_proj"))
-    if not all(isinstance(p, qlinear) for p in (g, u, d)) or activation_kind(getattr(mlp, "act_fn", None)) != "gelu_tanh":
+    if not all(is_code_fed(p) for p in (g, u, d)) or activation_kind(getattr(mlp, "act_fn", None)) != "gelu_tanh":
         return None
     if g.in_features != u.in_features or g.out_features != u.out_features or d.in_features != g.out_features or (g.bias is None) != (u.bias is None):
         return None

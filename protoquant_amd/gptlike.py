@@ -28,7 +28,7 @@ from torch import nn
 
 from . import _lib as L
 from .llama import _FusedSlice
-from .qlinear import FusedQLinear, qlinear
+from .qlinear import FusedQLinear, is_code_fed, qlinear
 from .qtensor import act_quantize, add2_layernorm_quantize, add_layernorm_quantize, layernorm_quantize, layernorm_quantize2
 from .residual_flow import _H, FlowPlan, FusedLayer, _hooked, _ProbeRefused, fuse_stacks
 
@@ -124,7 +124,7 @@ def _is_eligible_layernorm(m) -> bool:
 
 
 def _is_int8_proj(m) -> bool:
-    return isinstance(m, (qlinear, FusedQLinear, _FusedSlice))
+    return is_code_fed(m) or isinstance(m, (FusedQLinear, _FusedSlice))
 
 
 def _stateless(m: nn.Module) -> bool:
@@ -270,14 +270,14 @@ def fusable_activation(mlp: nn.Module):
     """(attribute name, kind) when `mlp` is act between two int8 projections: exactly one child module is an activation activation_kind() names, the MLP's own
     forward, run on the CPU against stand-ins, calls it once on the very tensor a projection returned, hands its output to exactly one projection and uses it for
     nothing else (a dropout between the two is a refusal).  None otherwise."""
-    if not any(isinstance(c, qlinear) for c in mlp.children()):
+    if not any(is_code_fed(c) for c in mlp.children()) or any(isinstance(c, qlinear) and not is_code_fed(c) for c in mlp.children()):
         return None
     cands = [(n, activation_kind(m)) for n, m in mlp.named_children() if not _is_int8_proj(m) and not isinstance(m, (nn.Dropout, ActQuant, LayerNormQuant)) and _stateless(m)]
     cands = [(n, k) for n, k in cands if k is not None]
     if len(cands) != 1:
         return None
     name, kind = cands[0]
-    first = next(c for c in mlp.children() if isinstance(c, qlinear))
+    first = next(c for c in mlp.children() if is_code_fed(c))
     rec = _Record()
     try:
         out = _run_probe(mlp, rec, acts={name: kind}, width=first.in_features)

@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .qlinear import FusedQLinear, GatedMLP, qlinear
+from .qlinear import FusedQLinear, GatedMLP, is_code_fed, qlinear
 from .qtensor import QTensor, add_rmsnorm_quantize, rmsnorm_quantize
 from .residual_flow import NamedFusedLayer, _forward_extra_params, attention, fuse_stacks, probe_named_flow
 from .residual_flow import _HandOver  # noqa: F401  (the name under which it was introduced here stays importable)
@@ -190,7 +190,7 @@ def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
         if attn is None or mlp is None or not hasattr(layer, "input_layernorm") or not hasattr(layer, "post_attention_layernorm"):
             continue
         q, k, v = (getattr(attn, p, None) for p in ("q_proj", "k_proj", "v_proj"))
-        if not all(isinstance(p, qlinear) for p in (q, k, v)):
+        if not all(is_code_fed(p) for p in (q, k, v)):
             continue
         if fuse_qkv:
             attn.qkv_fused = _SharedFused(FusedQLinear([q, k, v]))
@@ -198,7 +198,7 @@ def fuse_llama_layers(model: nn.Module, fuse_norms: bool = True, fuse_qkv: bool 
             _install_qkv_hooks(attn)
         if fuse_norms and _is_rmsnorm(layer.input_layernorm):
             layer.input_layernorm = RMSNormQuant(layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon)
-        mlp_ok = isinstance(mlp, GatedMLP) or all(isinstance(getattr(mlp, p, None), qlinear) for p in ("gate_proj", "up_proj"))
+        mlp_ok = isinstance(mlp, GatedMLP) or all(is_code_fed(getattr(mlp, p, None)) for p in ("gate_proj", "up_proj"))
         if fuse_norms and _is_rmsnorm(layer.post_attention_layernorm) and mlp_ok:
             layer.post_attention_layernorm = RMSNormQuant(layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon)
         n += 1

@@ -25,7 +25,7 @@ from torch import nn
 
 from .gemma import _NormStandin, _gemma_formula, _llama_formula
 from .llama import _FusedSlice, _SharedFused, _install_qkv_hooks
-from .qlinear import FusedQLinear, GatedMLP, qlinear
+from .qlinear import FusedQLinear, GatedMLP, is_code_fed
 from .qtensor import olmo_postnorm_add, olmo_postnorm_add_quantize, olmo_rmsnorm, quantize
 from .residual_flow import NamedFusedLayer, _forward_extra_params, _hooked, attention, fuse_stacks, probe_named_flow
 
@@ -160,7 +160,7 @@ class PostNormFusedLayer(NamedFusedLayer):
 def _qkv_state(attn) -> str:
     """"plain": three qlinear projections; "fused": the three slices of one shared fused GEMM; "": anything else"""
     q, k, v = (getattr(attn, p, None) for p in ("q_proj", "k_proj", "v_proj"))
-    if all(isinstance(p, qlinear) for p in (q, k, v)):
+    if all(is_code_fed(p) for p in (q, k, v)):
         return "plain"
     if all(isinstance(p, _FusedSlice) for p in (q, k, v)) and isinstance(getattr(attn, "qkv_fused", None), _SharedFused):
         return "fused"

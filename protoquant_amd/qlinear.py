@@ -490,6 +490,13 @@ class qlinear(_KPadded, nn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
 
 
+def is_code_fed(m) -> bool:
+    """A qlinear whose GEMM another producer's codes may feed (RMSNormQuant's, silu_mul_quantize's, a fused q/k/v weight): every qlinear but a subclass that transforms
+    its input before quantising it (hadamard.RotatedQLinear sets `code_fed = False`: its weight is rotated, so only codes of the rotated activation fit it).  The fuse_*
+    entries ask this where they used to ask isinstance(m, qlinear), and so leave such a module — and what would have fed it — alone."""
+    return isinstance(m, qlinear) and getattr(m, "code_fed", True)
+
+
 class FusedQLinear(_KPadded, nn.Module):
     """Horizontal fusion of projections that share one input (q/k/v, gate/up): the int8 weights are concatenated
     along N, the activation is quantised ONCE and one GEMM launch fills all outputs (better tile count on 256 CUs
