@@ -302,6 +302,21 @@ int32_t pq_head_rmsnorm(const void* x, int64_t ld_xo, int64_t ld_xi, const void*
 int32_t pq_hadamard_quant_rows(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld_x, int32_t block, int8_t* q, int64_t ld_q, float* scale, void* h_out,
                                int64_t ld_h, void* stream);
 
+/* K1gh — the gated activation of an MLP in front of K1h, in ONE launch (hadamard_kernels.hip; QSPEC GH1): the `down` input of a gated MLP whose down
+ * projection is rotated.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify, ld = 2 cols).
+ * h0 = the gated activation AS STORED — act PQ_GATE_SILU: cast_rne(f32(cast_rne(silu(g))) * f32(u)), QSPEC S1-S5 (pq_silu_mul_quant_rowwise's h); PQ_GATE_GELU_TANH:
+ * GG1-GG3 (pq_gelu_mul_quant_rowwise's h) — then H1-H5 on the rows of h0 with `block` as pq_hadamard_quant_rows takes it.  q, scale and h_out (nullable, ld_h: the
+ * ROTATED activation, H4; h0 itself is never stored) are, bit for bit, those of pq_hadamard_quant_rows run on the h_out of the gate's own entry.  There is no
+ * transform-only form.  Layouts as pq_hadamard_quant_rows (u counts among the operands that must be 16-byte aligned for the register layouts); the division-free
+ * quotient of the gate is chosen once per wave, time only, never bits.  No workspace, no atomics, one launch, graph-capturable.
+ * q, scale and h_out may overlap neither g, u nor each other.  An unknown dtype or act, a block that is no power of two in 2 .. 4096 or does not divide cols, a null
+ * g / u / q / scale, negative sizes, rows >= 2^31 and ld < cols are PQ_ERR_BAD_ARG before any HIP call, with pq_last_error naming the argument.  rows == 0 or
+ * cols == 0: nothing is read or written, returns PQ_OK. */
+#define PQ_GATE_SILU 0
+#define PQ_GATE_GELU_TANH 1
+int32_t pq_gated_hadamard_quant_rows(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t act, int32_t block,
+                                     int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream);
+
 /* K1gg— K1 fused into the tanh-GELU gate of a gated MLP (Gemma's down(act_fn(gate(x)) * up(x)), act_fn = gelu_pytorch_tanh): quantize(gelu_tanh(g) * u) per token in
  * one pass.  g, u: [rows, cols] of `dtype` with leading dimensions of their own (the column halves of one fused gate+up output qualify).  Numerics, QSPEC GG1-GG3:
  * a = cast_rne(gelu_tanh(f32(g))) with the tanh GELU of pq_act_quant_rowwise (QSPEC U2: NaN -> NaN, +Inf -> +Inf, -Inf -> -0), h = cast_rne(f32(a) * f32(u)), then Q1-Q6

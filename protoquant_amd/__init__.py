@@ -10,7 +10,7 @@ from .llama import RMSNormQuant, fuse_llama_layers
 from .gemma import GemmaRMSNormQuant, GemmaSandwichNormQuant, SandwichFusedLayer, fuse_gemma_layers, fuse_gemma_postnorm_residual, is_gemma_rmsnorm, residual_flow_is_sandwich
 from .olmo import OlmoRMSNorm, PostNormFusedLayer, fuse_olmo_layers, is_olmo_rmsnorm, residual_flow_is_postnorm
 from .qk_norm import HeadRMSNorm, fuse_qk_norms, head_norm_kind
-from .hadamard import RotatedQLinear, hadamard, hadamard_quantize, rotate_linears
+from .hadamard import RotatedQLinear, gated_hadamard_quantize, hadamard, hadamard_quantize, rotate_gated_mlps, rotate_linears
 from .granite import ScaledResidualFusedLayer, fuse_granite_residual, residual_flow_is_scaled
 from .sharded import (ColumnShardedGatedMLP, ColumnShardedQLinear, RcclColumnGather, RcclRowReduceScatter, RowShardedQLinear, ShardedGatedMLP,
                       gather_columns, gather_columns_overlapped, gather_rows_t, reduce_rows, shard_bounds)
@@ -27,5 +27,5 @@ __all__ = ["QTensor", "quantize", "dequantize", "qlinear", "qlinear_s8", "qlinea
            "olmo_postnorm_add_quantize", "olmo_postnorm_add", "olmo_rmsnorm", "OlmoRMSNorm", "PostNormFusedLayer", "fuse_olmo_layers", "is_olmo_rmsnorm", "residual_flow_is_postnorm",
            "scaled_add_rmsnorm_quantize", "scaled_add", "ScaledResidualFusedLayer", "fuse_granite_residual", "residual_flow_is_scaled",
            "head_rmsnorm", "HeadRMSNorm", "fuse_qk_norms", "head_norm_kind",
-           "hadamard", "hadamard_quantize", "RotatedQLinear", "rotate_linears",
+           "hadamard", "hadamard_quantize", "RotatedQLinear", "rotate_linears", "gated_hadamard_quantize", "rotate_gated_mlps",
            "moe_topk", "fuse_moe_routers", "router_parts", "RouterParts"]

@@ -16,6 +16,7 @@ PQ_BF16, PQ_FP16, PQ_F32 = 0, 1, 2
 GLU_KINDS = {"clamped_silu": 0, "alpha_sigmoid": 1}        # PQ_GLU_* of include/pq_hip.h
 ACT_KINDS = {"relu": 0, "gelu_tanh": 1, "gelu_erf": 2}     # PQ_ACT_* of include/pq_hip.h
 GAIN_KINDS = {"llama": 0, "gemma": 1}                      # PQ_GAIN_* of include/pq_hip.h
+GATE_KINDS = {"silu": 0, "gelu_tanh": 1}                   # PQ_GATE_* of include/pq_hip.h
 ROUTER_KINDS = {"softmax_topk": 0, "topk_softmax": 1}      # PQ_ROUTER_* of include/pq_hip.h
 _DT = {torch.bfloat16: PQ_BF16, torch.float16: PQ_FP16, torch.float32: PQ_F32}
 
@@ -86,6 +87,7 @@ SIGNATURES = {
     "pq_scaled_add_rmsnorm_quant_rows": (i32, [vp, i64, vp, i64, f32, vp, i64, vp, f32, i32, i64, i64, vp, i64, vp, vp, i64, vp]),
     "pq_head_rmsnorm": (i32, [vp, i64, i64, vp, f32, i32, i32, i64, i64, i64, vp, i64, i64, vp]),
     "pq_hadamard_quant_rows": (i32, [vp, i32, i64, i64, i64, i32, vp, i64, vp, vp, i64, vp]),
+    "pq_gated_hadamard_quant_rows": (i32, [vp, i64, vp, i64, i32, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp]),
     "pq_moe_topk": (i32, [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]),
 }
 EXPORTS = tuple(SIGNATURES)

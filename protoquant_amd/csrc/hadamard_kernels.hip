@@ -20,9 +20,17 @@
 // Generic form (any other legal block / cols / alignment, rows too long for registers): one workgroup per row, one block at a time transformed in LDS; with codes asked
 // for the row is transformed twice (the amax, then the codes: the second read comes from cache).  Same bits.
 // Aliasing: none (pq_api.hip refuses every overlap), so every pointer is __restrict__.
+//
+// K1gh (QSPEC GH1): the same kernels with the gated activation of an MLP as the PRODUCER of the row — h0 = cast(cast(silu(g)) * u) (S1-S5) or the tanh-GELU gate (GG1-GG3)
+// AS STORED, then H1-H5 on h0.  The work split, HadMap and the swizzles are K1h's, which is what keeps the rotation's bits.  Wave form: step 1 issues ALL its unit-stride
+// 16-byte loads of g and of u (2 NV in flight; each operand has a leading dimension of its own), takes the division-free quotient or `/` once per wave from the min / max
+// of the gate bits it loaded (K1s's test; both give the specification's bits), turns every pair of vectors into the stored h0 vector (silu_mul_vec / GegluOp::vec, the
+// instruction sequences of K1s / K1gg) and writes THAT to the raw LDS region; from the first barrier on the kernel is K1h.  Only the loaded vectors are live while the
+// producer runs, before the 64-float register array exists.  Generic form: the element load becomes the one-element producer (map_one around the same stage, then the
+// storage rounding).  h0 is never stored; h_out holds the ROTATED activation.
 #include <cmath>
 #include <type_traits>
-#include "quant_device.h"
+#include "geglu_device.h"
 #include "pq_launch.h"
 
 namespace pq {
@@ -30,7 +38,23 @@ namespace pq {
 constexpr int kLaneElems = 64;                            // consecutive elements a lane owns
 constexpr int kRegionBytes = kWave * kLaneElems * 4;      // one wave's LDS: its 4096 values as f32
 constexpr int kHadMaxWaves = 8;                           // waves per row of the wave form
-typedef float v2f __attribute__((ext_vector_type(2)));
+
+// the producer in front of the loads: kNoGate is K1h itself (u is never read), PQ_GATE_SILU / PQ_GATE_GELU_TANH are K1gh.  fast_ok: the wave's test on the min / max of
+// the |g| bit patterns; vec: one 16-byte vector of g and of u -> one of h0 as stored; one: the specified sequence on one element, before the storage rounding.
+constexpr int kNoGate = -1;
+template <int ACT> struct Gate;
+template <> struct Gate<PQ_GATE_SILU> {
+    template <int DT> __device__ static __forceinline__ bool fast_ok(uint32_t mn, uint32_t mx) { return silu_fast_div_ok<DT>(mn, mx); }
+    template <int DT, bool FASTDIV> __device__ static __forceinline__ v4u vec(const v4u& gv, const v4u& uv) { return silu_mul_vec<DT, FASTDIV>(gv, uv); }
+    template <int DT> __device__ static __forceinline__ float one(float g, float u) {
+        return map_one(g, u, [](const auto& ga, const auto& ua, auto& h) { silu_mul_stage<DT, false, 1>(ga, ua, h); });
+    }
+};
+template <> struct Gate<PQ_GATE_GELU_TANH> {
+    template <int DT> __device__ static __forceinline__ bool fast_ok(uint32_t mn, uint32_t mx) { return GegluOp::fast_ok<DT>(mn, mx, {}); }
+    template <int DT, bool FASTDIV> __device__ static __forceinline__ v4u vec(const v4u& gv, const v4u& uv) { return GegluOp::vec<DT, FASTDIV>(gv, uv, {}); }
+    template <int DT> __device__ static __forceinline__ float one(float g, float u) { return GegluOp::spec<DT>(g, u, {}); }
+};
 
 // byte offset -> swizzled byte offset in a wave's region seen as 64 lane rows of NV 16-byte granules (NV = 4: codes, 8: 16-bit values, 16: f32).  Granule `col` of row
 // `row` lies at column col ^ ((row / (16 / NV)) % NV): 16 consecutive lanes reading (or writing) the same column of their own rows, and 16 consecutive lanes walking
@@ -119,10 +143,11 @@ __device__ __forceinline__ void fwht_stages(float (&v)[N]) {
 }
 
 // LOGP: log2(block / 64).  multi: the row spans the waves of the workgroup (one row per workgroup); otherwise every wave holds 64 >> log_g rows of its own.
-template <int DT, int LOGP>
-__global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const uint8_t* __restrict__ x, int64_t ldx_bytes, int64_t rows, int slots, int log_g, int multi,
-                                                                          float c, int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale,
-                                                                          uint8_t* __restrict__ h_out, int64_t ldh_bytes) {
+// ACT: the producer (kNoGate: x is the row, u / ldu_bytes are not read; otherwise x is the gate g).
+template <int DT, int LOGP, int ACT>
+__global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const uint8_t* __restrict__ x, int64_t ldx_bytes, const uint8_t* __restrict__ u, int64_t ldu_bytes,
+                                                                          int64_t rows, int slots, int log_g, int multi, float c, int8_t* __restrict__ q, int64_t ldq,
+                                                                          float* __restrict__ scale, uint8_t* __restrict__ h_out, int64_t ldh_bytes) {
     constexpr int EB = Elem<DT>::kBytes, EPV = 16 / EB, NV = kLaneElems / EPV;      // NV: 16-byte vectors per lane (8 / 16)
     constexpr int P = 1 << LOGP, RL = kLaneElems / P;
     extern __shared__ v4u had_lds[];
@@ -135,6 +160,7 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
 
     // ---- 1. unit-stride loads (clamped: a lane row past the data reads slot 0 of the last row and is zeroed by its owner), raw through LDS
     v4u raw[NV];
+    [[maybe_unused]] v4u uraw[ACT == kNoGate ? 1 : NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int g = k * kWave + lane;
@@ -144,18 +170,35 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
         m.at(g / NV, row, t, valid);
         if (!valid) { row = row < rows ? row : rows - 1; t = 0; }
         raw[k] = *reinterpret_cast<const v4u*>(x + row * ldx_bytes + ((int64_t)t * NV + g % NV) * 16);
+        if constexpr (ACT != kNoGate) uraw[k] = *reinterpret_cast<const v4u*>(u + row * ldu_bytes + ((int64_t)t * NV + g % NV) * 16);
     }
+    if constexpr (ACT != kNoGate) {          // K1gh: raw becomes the stored h0; the quotient's form is the wave's (K1s's test on the gate bits loaded, clamped ones included)
+        uint32_t gmn = 0xFFFFFFFFu, gmx = 0u;
 #pragma unroll
-    for (int k = 0; k < NV; ++k) *reinterpret_cast<v4u*>(region + swz<NV>((uint32_t)(k * kWave + lane) * 16u)) = raw[k];
+        for (int k = 0; k < NV; ++k) vec_absminmax_bits<DT>(raw[k], gmn, gmx);
+        if (__builtin_amdgcn_ballot_w64(!Gate<ACT>::template fast_ok<DT>(gmn, gmx)) == 0ull) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) raw[k] = Gate<ACT>::template vec<DT, true>(raw[k], uraw[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) raw[k] = Gate<ACT>::template vec<DT, false>(raw[k], uraw[k]);
+        }
+    }
+    // K1gh: the lane index from here on is a value of its own, so that the row / slot / validity arithmetic of the stores at the kernel's end is redone there instead of
+    // being kept live (and spilled) across the producer, whose 2 NV loaded vectors fill the register file of an f32 row
+    int ln = lane;
+    if constexpr (ACT != kNoGate) asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int k = 0; k < NV; ++k) *reinterpret_cast<v4u*>(region + swz<NV>((uint32_t)(k * kWave + ln) * 16u)) = raw[k];
     __syncthreads();
     int64_t my_row;
     int my_t;
     bool my_valid;
-    m.at(lane, my_row, my_t, my_valid);      // (the P lanes of a block are valid together: cols is a multiple of the block)
+    m.at(ln, my_row, my_t, my_valid);      // (the P lanes of a block are valid together: cols is a multiple of the block)
     float v[kLaneElems];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        v4u r = *reinterpret_cast<const v4u*>(region + swz<NV>((uint32_t)(lane * NV + k) * 16u));
+        v4u r = *reinterpret_cast<const v4u*>(region + swz<NV>((uint32_t)(ln * NV + k) * 16u));
         if (!my_valid) r = v4u{0u, 0u, 0u, 0u};
         float f[EPV];
         Unpack<DT, EPV>::run(r, f);          // H1
@@ -164,14 +207,14 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
     }
     // ---- 2. stages 0 .. 5
     fwht_stages<1>(v);
-    // ---- 3. lane bits <-> register bits, stages 6 ..
+    // ---- 3. ln bits <-> register bits, stages 6 ..
     if constexpr (LOGP > 0) {
         __syncthreads();                     // every raw read of this region is done
 #pragma unroll
         for (int ch = 0; ch < 16; ++ch)
-            *reinterpret_cast<v4f*>(region + lane * 256 + ((ch ^ tswz<P>(lane)) << 4)) = v4f{v[4 * ch], v[4 * ch + 1], v[4 * ch + 2], v[4 * ch + 3]};
+            *reinterpret_cast<v4f*>(region + ln * 256 + ((ch ^ tswz<P>(ln)) << 4)) = v4f{v[4 * ch], v[4 * ch + 1], v[4 * ch + 2], v[4 * ch + 3]};
         __syncthreads();
-        const uint32_t pp = lane & (P - 1), first = lane & ~(P - 1);
+        const uint32_t pp = ln & (P - 1), first = ln & ~(P - 1);
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const uint32_t row = first + p;
@@ -207,7 +250,7 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
             if (off < (1 << log_g)) amax = amax_merge(amax, __shfl_xor(amax, off, 64));
         if (multi) {
             float* part = reinterpret_cast<float*>(had_lds);
-            if (lane == 0) part[wave] = amax;
+            if (ln == 0) part[wave] = amax;
             __syncthreads();
             for (int w = 0; w < nwaves; ++w) amax = amax_merge(amax, part[w]);
             __syncthreads();
@@ -222,9 +265,9 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
             for (int j = 0; j < kLaneElems / 4; ++j) pk[j] = pack4(code_of(v[4 * j], s), code_of(v[4 * j + 1], s), code_of(v[4 * j + 2], s), code_of(v[4 * j + 3], s));
         }
         // ---- 5. the codes back to the unit-stride order
-        scatter_runs<4, P>(region, lane, pk);
+        scatter_runs<4, P>(region, ln, pk);
         __syncthreads();
-        gather_store<4>(region, lane, m, reinterpret_cast<uint8_t*>(q), ldq);
+        gather_store<4>(region, ln, m, reinterpret_cast<uint8_t*>(q), ldq);
     }
     if (h_out) {
         if (q) __syncthreads();
@@ -234,26 +277,31 @@ __global__ __launch_bounds__(64 * kHadMaxWaves) void hadamard_quant_wave(const u
             if constexpr (EB == 4) hw[j] = __builtin_bit_cast(uint32_t, v[j]);
             else hw[j] = (uint32_t)Elem<DT>::from_f32(v[2 * j]) | ((uint32_t)Elem<DT>::from_f32(v[2 * j + 1]) << 16);      // (exact: v holds storage values)
         }
-        scatter_runs<NV, P>(region, lane, hw);
+        scatter_runs<NV, P>(region, ln, hw);
         __syncthreads();
-        gather_store<NV>(region, lane, m, h_out, ldh_bytes);
+        gather_store<NV>(region, ln, m, h_out, ldh_bytes);
     }
 }
 
 // one workgroup per row, one block at a time in LDS; thread t owns elements t, t + 256, .. of a block outside the stages
-template <int DT>
-__global__ __launch_bounds__(256) void hadamard_quant_generic(const void* __restrict__ x, int64_t ldx, int64_t cols, int block, int log_b, float c, int8_t* __restrict__ q,
-                                                              int64_t ldq, float* __restrict__ scale, void* __restrict__ h_out, int64_t ldh) {
+template <int DT, int ACT>
+__global__ __launch_bounds__(256) void hadamard_quant_generic(const void* __restrict__ x, int64_t ldx, const void* __restrict__ u, int64_t ldu, int64_t cols, int block,
+                                                              int log_b, float c, int8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale, void* __restrict__ h_out,
+                                                              int64_t ldh) {
     using S = typename Elem<DT>::store_t;
     __shared__ float buf[4096];
     __shared__ float part[4];
     const int64_t row = blockIdx.x;
     const S* xr = reinterpret_cast<const S*>(x) + row * ldx;
+    [[maybe_unused]] const S* ur = reinterpret_cast<const S*>(u) + row * ldu;
     S* hr = h_out ? reinterpret_cast<S*>(h_out) + row * ldh : nullptr;
     const int tid = threadIdx.x;
     const auto transform = [&](int64_t c0) {      // leaves h as stored (widened) in buf; a thread reads back only what it wrote last
         __syncthreads();
-        for (int i = tid; i < block; i += 256) buf[i] = Elem<DT>::to_f32(xr[c0 + i]);
+        for (int i = tid; i < block; i += 256) {
+            if constexpr (ACT == kNoGate) buf[i] = Elem<DT>::to_f32(xr[c0 + i]);
+            else buf[i] = Elem<DT>::to_f32(Elem<DT>::from_f32(Gate<ACT>::template one<DT>(Elem<DT>::to_f32(xr[c0 + i]), Elem<DT>::to_f32(ur[c0 + i]))));      // h0 as stored
+        }
         __syncthreads();
         for (int s = 0; s < log_b; ++s) {
             for (int idx = tid; idx < block / 2; idx += 256) {
@@ -289,17 +337,18 @@ __global__ __launch_bounds__(256) void hadamard_quant_generic(const void* __rest
     }
 }
 
-template <int DT>
-hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int64_t cols, int block, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh,
-                                   hipStream_t st) {
+// the layout decision of K1h and K1gh, made once (u / ldu: K1gh's second operand, null / 0 for K1h)
+template <int DT, int ACT>
+static hipError_t hadamard_dispatch(const void* x, int64_t ldx, const void* u, int64_t ldu, int64_t rows, int64_t cols, int block, int8_t* q, int64_t ldq, float* scale,
+                                    void* h_out, int64_t ldh, hipStream_t st) {
     constexpr int64_t EB = Elem<DT>::kBytes;
     int log_b = 0;
     while ((1 << log_b) < block) ++log_b;
     const float c = (float)(1.0 / std::sqrt((double)block));      // H3: exact for even log2 B, the nearest binary32 otherwise
     const auto rows16 = [&](const void* p, int64_t ld_bytes) { return !p || (aligned_to(p, 16) && (rows == 1 || ld_bytes % 16 == 0)); };
-    const bool wave_ok = block >= kLaneElems && cols <= (int64_t)kHadMaxWaves * kWave * kLaneElems && rows16(x, ldx * EB) && rows16(q, ldq) && rows16(h_out, ldh * EB);
+    const bool wave_ok = block >= kLaneElems && cols <= (int64_t)kHadMaxWaves * kWave * kLaneElems && rows16(x, ldx * EB) && rows16(u, ldu * EB) && rows16(q, ldq) && rows16(h_out, ldh * EB);
     if (!wave_ok) {
-        hadamard_quant_generic<DT><<<dim3((unsigned)rows), dim3(256), 0, st>>>(x, ldx, cols, block, log_b, c, q, ldq, scale, h_out, ldh);
+        hadamard_quant_generic<DT, ACT><<<dim3((unsigned)rows), dim3(256), 0, st>>>(x, ldx, u, ldu, cols, block, log_b, c, q, ldq, scale, h_out, ldh);
         return hipSuccess;
     }
     const int slots = (int)(cols / kLaneElems);
@@ -314,11 +363,11 @@ hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int
     hipError_t err = hipSuccess;
     const auto go = [&](auto lp) {
         constexpr int LOGP = decltype(lp)::value;
-        auto* kern = hadamard_quant_wave<DT, LOGP>;
+        auto* kern = hadamard_quant_wave<DT, LOGP, ACT>;
         if (lds >= 64 * 1024) err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return;
-        kern<<<grid, threads, lds, st>>>(reinterpret_cast<const uint8_t*>(x), ldx * EB, rows, slots, log_g, multi ? 1 : 0, c, q, ldq, scale,
-                                        reinterpret_cast<uint8_t*>(h_out), ldh * EB);
+        kern<<<grid, threads, lds, st>>>(reinterpret_cast<const uint8_t*>(x), ldx * EB, reinterpret_cast<const uint8_t*>(u), ldu * EB, rows, slots, log_g, multi ? 1 : 0, c,
+                                        q, ldq, scale, reinterpret_cast<uint8_t*>(h_out), ldh * EB);
     };
     switch (log_b - 6) {
         case 0: go(std::integral_constant<int, 0>{}); break;
@@ -332,8 +381,24 @@ hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int
     return err;
 }
 
+template <int DT>
+hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int64_t cols, int block, int8_t* q, int64_t ldq, float* scale, void* h_out, int64_t ldh,
+                                   hipStream_t st) {
+    return hadamard_dispatch<DT, kNoGate>(x, ldx, nullptr, 0, rows, cols, block, q, ldq, scale, h_out, ldh, st);
+}
+template <int DT>
+hipError_t gated_hadamard_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, int act, int block, int8_t* q, int64_t ldq,
+                                         float* scale, void* h_out, int64_t ldh, hipStream_t st) {
+    if (act == PQ_GATE_GELU_TANH) return hadamard_dispatch<DT, PQ_GATE_GELU_TANH>(g, ldg, u, ldu, rows, cols, block, q, ldq, scale, h_out, ldh, st);
+    return hadamard_dispatch<DT, PQ_GATE_SILU>(g, ldg, u, ldu, rows, cols, block, q, ldq, scale, h_out, ldh, st);
+}
+
 template hipError_t hadamard_quant_dispatch<PQ_BF16>(const void*, int64_t, int64_t, int64_t, int, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 template hipError_t hadamard_quant_dispatch<PQ_FP16>(const void*, int64_t, int64_t, int64_t, int, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
 template hipError_t hadamard_quant_dispatch<PQ_F32>(const void*, int64_t, int64_t, int64_t, int, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+#define PQ_GH_INST(DT) \
+    template hipError_t gated_hadamard_quant_dispatch<DT>(const void*, int64_t, const void*, int64_t, int64_t, int64_t, int, int, int8_t*, int64_t, float*, void*, int64_t, hipStream_t);
+PQ_GH_INST(PQ_BF16) PQ_GH_INST(PQ_FP16) PQ_GH_INST(PQ_F32)
+#undef PQ_GH_INST
 
 }  // namespace pq

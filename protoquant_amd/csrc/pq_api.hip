@@ -690,6 +690,27 @@ int32_t pq_hadamard_quant_rows(const void* x, int32_t dtype, int64_t rows, int64
     return check_launch(fn);
 }
 
+int32_t pq_gated_hadamard_quant_rows(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t act, int32_t block,
+                                     int8_t* q, int64_t ld_q, float* scale, void* h_out, int64_t ld_h, void* stream) {
+    Range range_("pq:gated_hadamard_quant (K1gh)");
+    const char* fn = "pq_gated_hadamard_quant_rows";
+    if (const int32_t rc = check_dtype(fn, dtype)) return rc;
+    if (act != PQ_GATE_SILU && act != PQ_GATE_GELU_TANH) return fail(PQ_ERR_BAD_ARG, "%s: unknown act %d (0 = silu, 1 = gelu_tanh)", fn, act);
+    if (block < 2 || block > 4096 || (block & (block - 1)) != 0) return fail(PQ_ERR_BAD_ARG, "%s: block must be a power of two, 2 .. 4096 (block=%d)", fn, block);
+    if (cols > 0 && cols % block != 0) return fail(PQ_ERR_BAD_ARG, "%s: block %d does not divide cols %lld", fn, block, (long long)cols);
+    if (rows > (int64_t)INT32_MAX) return fail(PQ_ERR_BAD_ARG, "%s: rows must be < 2^31 (rows=%lld)", fn, (long long)rows);
+    const int64_t eb = dtype == PQ_F32 ? 4 : 2;
+    const char* note = " (this entry has no transform-only form)";
+    const RowOperand ops[] = {{"g", g, R_IN, "ld_g", ld_g, eb, ""},           {"u", u, R_IN, "ld_u", ld_u, eb, ""}, {"q", q, R_OUT, "ld_q", ld_q, 1, note},
+                              {"scale", scale, R_OUT, nullptr, rows, 4, note}, {"h_out", h_out, R_OUT, "ld_h", ld_h, eb, nullptr}};
+    bool empty;
+    if (const int32_t rc = check_row_producer(fn, rows, cols, nullptr, ops, 5, &empty); rc || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e = by_dtype(dtype, [&](auto dt) { return pq::gated_hadamard_quant_dispatch<dt>(g, ld_g, u, ld_u, rows, cols, act, block, q, ld_q, scale, h_out, ld_h, st); });
+    if (e != hipSuccess) return fail(PQ_ERR_LAUNCH, "%s: sizing the LDS of the launch: %s", fn, hipGetErrorString(e));
+    return check_launch(fn);
+}
+
 int32_t pq_gelu_mul_quant_rowwise(const void* g, int64_t ld_g, const void* u, int64_t ld_u, int32_t dtype, int64_t rows, int64_t cols, int32_t kind, int8_t* q, int64_t ld_q,
                                   float* scale, void* h_out, int64_t ld_h, void* stream) {
     Range range_("pq:gelu_mul_quant (K1gg)");

@@ -64,6 +64,9 @@ template <int DT> void gelu_mul_quant_dispatch(const void* g, int64_t ldg, const
 // host call in front of the launch (the LDS size of a row of more than 12 288 elements), hipSuccess otherwise
 template <int DT> hipError_t hadamard_quant_dispatch(const void* x, int64_t ldx, int64_t rows, int64_t cols, int block, int8_t* q, int64_t ldq, float* scale, void* h_out,
                                                      int64_t ldh, hipStream_t st);
+// K1gh: the gated activation (act: PQ_GATE_SILU / PQ_GATE_GELU_TANH) of g and u as stored, then K1h on it — the same kernels with a producer in front of their loads
+template <int DT> hipError_t gated_hadamard_quant_dispatch(const void* g, int64_t ldg, const void* u, int64_t ldu, int64_t rows, int64_t cols, int act, int block, int8_t* q,
+                                                           int64_t ldq, float* scale, void* h_out, int64_t ldh, hipStream_t st);
 
 // ---- the GEMMs (K3 + K4): gemm_s8_generic.hip, gemm_s8_skinny.hip, gemm_s8_ring.hip, gemm_s8_fast.hip
 template <int OUT> void launch_gemm_generic(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb, const EpiArgs& epi, int64_t M, int64_t N, int64_t K, hipStream_t st);

@@ -4,22 +4,29 @@ the weight is rotated once, when the layer is swapped.  Calibration-free and exa
 
     hadamard(x, block)            the rotation alone (kernel K1h, transform-only form)
     hadamard_quantize(x, block)   the rotation and the per-token quantisation in ONE pass (K1h) — quantize(hadamard(x)) bit for bit (QSPEC H1-H5)
-    RotatedQLinear                a qlinear whose weight is rotated and whose forward rotates + quantises its input with hadamard_quantize
+    gated_hadamard_quantize(g, u, act, block)   the gated activation of an MLP, its rotation and its quantisation in ONE pass (K1gh) — hadamard_quantize of
+                                  silu_mul_quantize's / gelu_mul_quantize's h, bit for bit (QSPEC GH1)
+    RotatedQLinear                a qlinear whose weight is rotated and whose forward rotates + quantises its input with hadamard_quantize; forward_rotated takes
+                                  codes of the rotated activation (gated_hadamard_quantize's)
     rotate_linears(model, ..)     opt-in: chosen nn.Linear -> RotatedQLinear
+    rotate_gated_mlps(model, ..)  opt-in: a Llama-shaped MLP -> GatedMLP(fused gate+up, RotatedQLinear down): gate+up GEMM -> K1gh -> down GEMM
 
-Call order: rotate_linears first, for the chosen layers (typically down_proj, whose input carries the outlier channels); then swap_linears for the rest; then the fuse_*
-entries.  Those leave a RotatedQLinear alone (qlinear.is_code_fed): its input is NOT taken into a fused producer — a rotated down_proj gets the stock MLP's float
-activation and runs K1h itself (silu_mul_quantize cannot feed it), rotated q/k/v projections are not fused into one GEMM, and a norm in front of a rotated projection
-stays the eager norm.  There is no CPU path.  Out of scope: rotating the residual stream offline, fusing the rotation into the norm / activation producers,
-non-power-of-two Hadamard factors, the sharded modules, GroupedQLinear, convert_checkpoint."""
+Call order: rotate_gated_mlps (whole MLPs whose down_proj is to be rotated) and / or rotate_linears (single layers) first; then swap_linears for the rest; then the
+fuse_* entries.  Those leave a RotatedQLinear alone (qlinear.is_code_fed): its input is NOT taken into a fused producer.  What stays unfused: a down_proj rotated by
+rotate_linears alone (not as part of a GatedMLP) gets the stock MLP's float activation and runs K1h itself, rotated q/k/v projections are not fused into one GEMM, and a
+norm in front of a rotated projection stays the eager norm.  A GatedMLP built by rotate_gated_mlps has no torch arithmetic inside: fuse_llama_layers accepts it as it
+accepts every GatedMLP, so both norms of the layer still fuse.  There is no CPU path.  Out of scope: rotating the residual stream offline, an RMSNorm / LayerNorm
+producer in front of rotated gate/up or q/k/v projections (its pinned summation order is tied to K1n's layout), fuse_gemma_layers recognising a rotated GeGLU (the
+gelu_tanh kind is reachable through gated_hadamard_quantize and a hand-built GatedMLP(act="gelu_tanh") only), the clamped MoE gates and GroupedQLinear,
+non-power-of-two Hadamard factors, the sharded modules, convert_checkpoint."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
 from . import _lib as L
-from .qlinear import is_plain_linear, qlinear
-from .qtensor import QTensor, _alloc, _check_out, _launch, _on_gpu, _pack, _ptr, _rows_view, _rows_view_of_out, quantize
+from .qlinear import FusedQLinear, GatedMLP, _is_silu, is_plain_linear, qlinear
+from .qtensor import QTensor, _alloc, _check_match, _check_out, _launch, _on_gpu, _pack, _ptr, _rows_view, _rows_view_of_out, quantize
 
 MIN_BLOCK, MAX_BLOCK = 16, 4096
 
@@ -81,6 +88,26 @@ def hadamard_quantize(x: torch.Tensor, block: int | None = None, return_h: bool 
     return _pack(x, q, scale, h)
 
 
+def gated_hadamard_quantize(g: torch.Tensor, u: torch.Tensor, act: str = "silu", block: int | None = None, return_h: bool = False):
+    """hadamard_quantize(h0, block) for h0 = the gated activation of g and u as stored — act "silu": silu_mul_quantize's h (QSPEC S1-S5), "gelu_tanh": gelu_mul_quantize's
+    (GG1-GG3) — in ONE pass (kernel K1gh): h0 is computed in registers in front of K1h's first LDS pass and never goes to HBM.  Codes and scales are those of the
+    two-launch composition bit for bit (QSPEC GH1).  g and u have the same shape and dtype and may be the column halves of one fused gate+up output.  return_h=True also
+    returns the ROTATED activation hadamard(h0, block) (stored by the same kernel; h0 itself is never stored).  `block` as hadamard."""
+    what = "gated_hadamard_quantize"
+    _on_gpu(what, g=g, u=u)
+    if act not in L.GATE_KINDS:
+        raise ValueError(f"{what}: unknown act {act!r}, expected one of {sorted(L.GATE_KINDS)}")
+    _check_match(what, "g", g, "u", u, devices=False)
+    code = L.dtype_code(g.dtype)
+    block = _block_of(what, g.shape[-1], block)
+    g2, u2 = _rows_view(g), _rows_view(u)
+    rows, cols = g2.shape
+    q, scale, h = _alloc(rows, cols, g, return_h, host_ones_when_empty=True)
+    _launch(what, g.device, L.lib().pq_gated_hadamard_quant_rows, g2.data_ptr(), L.ld(g2), u2.data_ptr(), L.ld(u2), code, rows, cols, L.GATE_KINDS[act], block, q.data_ptr(),
+            max(cols, 1), scale.data_ptr(), _ptr(h), max(cols, 1), L.stream_ptr(g))
+    return _pack(g, q, scale, h)
+
+
 class RotatedQLinear(qlinear):
     """A qlinear on the rotated problem: `wq` / `ws` hold the per-channel quantisation of W R (R = diag(H_block) / sqrt(block) along in_features) and forward quantises
     x R with hadamard_quantize, so y approximates x W^T as qlinear does, with the outlier channels of x spread over their blocks first.  The block lives in the persistent
@@ -129,6 +156,13 @@ class RotatedQLinear(qlinear):
             raise ValueError(f"RotatedQLinear: expected last dim {self.in_features}, got {x.shape[-1]}")
         return super().forward(hadamard_quantize(x, self.block))
 
+    def forward_rotated(self, xq: QTensor) -> torch.Tensor:
+        """the GEMM alone on a per-token QTensor that the caller DECLARES to hold codes of the rotated activation x R with this layer's block (gated_hadamard_quantize's,
+        hadamard_quantize's): nothing here can tell them from other codes"""
+        if not isinstance(xq, QTensor):
+            raise TypeError("RotatedQLinear.forward_rotated: expected a per-token QTensor of the rotated activation; forward takes the float tensor")
+        return super().forward(xq)
+
     def extra_repr(self):
         return f"{super().extra_repr()}, rot_block={self.__dict__.get('_block', '?')}"
 
@@ -149,4 +183,34 @@ def rotate_linears(model: nn.Module, predicate=None, block: int | None = None) -
                 n += 1
         else:
             n += rotate_linears(child, predicate, block)
+    return n
+
+
+def _rotatable_mlp(mod: nn.Module, block):
+    """qlinear._as_gated_mlp's conditions (plain nn.Linear gate_proj / up_proj / down_proj, a SiLU act_fn, matching widths, gate and up both with or both without a
+    bias) and a legal block for the intermediate width: that block, or None"""
+    g, u, d = (getattr(mod, n, None) for n in ("gate_proj", "up_proj", "down_proj"))
+    if not all(is_plain_linear(l) for l in (g, u, d)) or not _is_silu(getattr(mod, "act_fn", None)):
+        return None
+    if g.in_features != u.in_features or g.out_features != u.out_features or d.in_features != g.out_features or (g.bias is None) != (u.bias is None):
+        return None
+    b = default_block(d.in_features) if block is None else block
+    return b if b >= MIN_BLOCK and d.in_features % b == 0 else None
+
+
+def rotate_gated_mlps(model: nn.Module, predicate=None, block: int | None = None) -> int:
+    """Replace every Llama-shaped MLP of `model` (in place) — what swap_linears(fuse_gated_mlp=True) would take — for which predicate(name, module) is true (None: all) and
+    whose intermediate width has a legal block (`block`, or None: the largest power of two dividing it, at most 4096, at least 16) by
+    GatedMLP(FusedQLinear.from_linears(gate, up), RotatedQLinear.from_linear(down, block)): one fused gate+up GEMM, K1gh (silu * mul, the rotation and the quantisation in
+    one launch), the down GEMM on the rotated weight.  Anything else is left untouched, object for object; returns the number replaced (a second call: 0).  Opt-in; call
+    it BEFORE swap_linears (which takes the remaining nn.Linear layers) and the fuse_* entries, as rotate_linears."""
+    n = 0
+    for name, child in list(model.named_children()):
+        b = _rotatable_mlp(child, block) if predicate is None or predicate(name, child) else None
+        if b is not None:
+            L.require_gpu(child.down_proj.weight, "rotate_gated_mlps(down_proj.weight)")      # (before anything is built: a CPU model is refused with the model unchanged)
+            setattr(model, name, GatedMLP(FusedQLinear.from_linears(child.gate_proj, child.up_proj), RotatedQLinear.from_linear(child.down_proj, b)))
+            n += 1
+        elif not isinstance(child, (qlinear, GatedMLP)):
+            n += rotate_gated_mlps(child, predicate, block)
     return n

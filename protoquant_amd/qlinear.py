@@ -541,7 +541,9 @@ class GatedMLP(nn.Module):
     """The gated MLP block of BASELINE config 3 on the int8 path: down(silu(gate(x)) * up(x)).
     gate and up share one activation quantisation and one GEMM launch (FusedQLinear); silu*mul is fused into the
     quantisation of down's input (silu_mul_quantize), so between the two GEMMs only int8 codes + row scales exist.
-    act="gelu_tanh" (Gemma's GeGLU; gemma.fuse_gemma_layers builds it) puts gelu_mul_quantize in silu_mul_quantize's place."""
+    act="gelu_tanh" (Gemma's GeGLU; gemma.fuse_gemma_layers builds it) puts gelu_mul_quantize in silu_mul_quantize's place.  A `down` that is a
+    hadamard.RotatedQLinear (hadamard.rotate_gated_mlps builds it) takes codes of the ROTATED activation: the gate, the rotation and the quantisation are one launch
+    (hadamard.gated_hadamard_quantize, kernel K1gh)."""
 
     ACTS = ("silu", "gelu_tanh")
 
@@ -559,6 +561,9 @@ class GatedMLP(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         g, u = self.gate_up(x)
+        if not getattr(self.down, "code_fed", True):          # a RotatedQLinear: only codes of the rotated activation fit its weight
+            from .hadamard import gated_hadamard_quantize
+            return self.down.forward_rotated(gated_hadamard_quantize(g, u, self.act, self.down.block))
         if self.act == "gelu_tanh":          # Gemma's GeGLU: down(gelu_tanh(gate(x)) * up(x)), kernel K1gg
             return self.down(gelu_mul_quantize(g, u))
         return self.down(silu_mul_quantize(g, u))
