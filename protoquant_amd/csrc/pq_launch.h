@@ -87,13 +87,12 @@ bool fsk_kslabs_ok(int64_t K, int64_t k_per_slab, int kslices);
 size_t fsk_workspace_bytes(int64_t M, int64_t N, int kslices);
 void set_stamp_buffer(unsigned long long* p);
 
-// ---- the grouped GEMMs of a mixture-of-experts layer (gemm_s8_grouped.hip, gemm_s8_grouped_stream.hip) and its routing / combine kernels (moe_kernels.hip)
+// ---- the grouped GEMMs of a mixture-of-experts layer (gemm_s8_grouped.hip; gemm_s8_grouped_stream.hip: with gemm_s8_skinny.hip one of the two hosts of the
+// weight-streaming body, gemm_stream_body.h — their planners are pq_plan.h's) and its routing / combine kernels (moe_kernels.hip)
 template <int OUT> void launch_gemm_grouped(int tile, const int8_t* X, int64_t ldx, const int32_t* qrow, int64_t x_rows, const int8_t* W, int64_t ldw, int64_t w_stride,
                                             const EpiArgs& epi, const int32_t* offsets, int E, int64_t M_total, int64_t N, int64_t K, int rot, hipStream_t st);
 template <int OUT> void launch_gemm_grouped_stream(const int8_t* X, int64_t ldx, const int32_t* qrow, int64_t x_rows, const int8_t* W, int64_t ldw, int64_t w_stride,
                                                    const EpiArgs& epi, const int32_t* offsets, int E, int64_t M_total, int64_t N, int64_t K, hipStream_t st);
-void grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t K, int* mt_out, int* rb_out, int* ks_out);
-const char* grouped_stream_plan_name(int mt, int rb, int ks);
 size_t moe_route_workspace_bytes(int64_t npairs, int E);
 void launch_moe_route(const void* ids, bool ids_are_int64, int64_t ld_ids, int64_t T, int k, int E, int32_t* offsets, int32_t* row_index, int32_t* rows_of, int32_t* slot_of,
                       const float* xs, float* xs_sorted, void* workspace, hipStream_t st);

@@ -19,6 +19,11 @@ int fsk_plan(int64_t M, int64_t N, int64_t K);
 Variant kslabs_in_place(const int8_t* a, int64_t lda, int64_t slab_stride, int64_t kps, const int8_t* b, int64_t ldb, int64_t M, int64_t N, int64_t K);
 int kslabs_fsk_in_place(const int8_t* a, int64_t lda, int64_t slab_stride, int64_t kps, const int8_t* b, int64_t ldb, int64_t M, int64_t N, int64_t K);
 int grouped_plan(int32_t E, int64_t M_total, int64_t N);
+// the weight-streaming decode kernels: one rule table (rows, N) -> (RB, waves per launch, least K split), asked with M by the dense kernel and with the average rows
+// of an expert slot by the grouped one
+void skinny_plan(int64_t M, int64_t N, int64_t K, int* rb_out, int* ks_out);
+void grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t K, int* mt_out, int* rb_out, int* ks_out);
+const char* grouped_stream_plan_name(int mt, int rb, int ks);
 
 // what pq_gemm_variant_name, pq_kslabs_way_name and pq_grouped_variant_name return (the caller has pinned the snapshot)
 const char* gemm_variant_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb);

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "gemm_stream_body.h"
 #include "pq_launch.h"
 #include "pq_plan.h"
 
@@ -207,7 +208,84 @@ int grouped_plan(int32_t E, int64_t M_total, int64_t N) {
     return mt * ((N + 63) / 64) <= device_cus() ? 1 : 0;
 }
 
+// ---- the weight-streaming decode kernels (gemm_stream_body.h): weight blocks per wave (RB) and the K split (KS, waves per workgroup) of a launch
+// Round 4 swept both over 19 decode-like shapes, weights from HBM (profiles/r04_skinny_sweep.txt); the rules below are that table's arg-min, within 3 % on every shape
+// (the round-3 rule — two blocks per wave from N = 6144 on, ~4096 waves per launch — was 5 - 21 % off on eleven of them):
+//   * one token: one block per wave, at least four waves per workgroup (the waves of a workgroup walk the SAME 16 weight rows at different K offsets: with one
+//     wave per workgroup thousands of rows are open at once, 64 bytes at a time — lm_head 115 us against 93), ~4096 waves per launch;
+//   * 2 .. 32 tokens (the activation fragments are real traffic): narrow matrices (N <= 4096) one block per wave and ~2048 waves; 4096 < N < 16384 two blocks per
+//     wave (every activation fragment reused twice) and only ~768 waves; from N = 16384 on one block per wave again, split in 4 (up to 8 tokens) or 2;
+//   * 33 .. 64 tokens (three or four token tiles; only against narrow matrices): one block per wave, ~4096 waves — unchanged.
+namespace {
+struct StreamRule { int rb, min_ks; int64_t target; };      // target: waves per launch
+StreamRule stream_rule(int64_t rows, int64_t N) {
+    if (rows == 1) return {1, 4, 4096};
+    if (rows > 32) return {1, 1, 4096};
+    if (N <= 4096) return {1, 2, 2048};
+    if (N < 16384) return {2, 2, 768};      // (from N = 4097 on: 16-row blocks of a 5120-wide matrix are 320 workgroups, a round and a quarter of the chip)
+    return {1, rows <= 8 ? 4 : 2, 1};
+}
+// always at least one k-step batch per wave, at most 16 waves per workgroup
+int stream_ks(const StreamRule& r, int64_t blocks, int64_t steps, int batch) {
+    int ks = 1;
+    while (ks < 16 && (blocks * ks < r.target || ks < r.min_ks) && steps / (ks * 2) >= batch) ks <<= 1;
+    return ks;
+}
+}  // namespace
+
+// the dense kernel: the rule of its M tokens over the blocks of one matrix.  PQ_SKINNY_RB / PQ_SKINNY_KS force either.
+void skinny_plan(int64_t M, int64_t N, int64_t K, int* rb_out, int* ks_out) {
+    const int mt = (int)((M + 15) / 16);
+    const StreamRule rule = stream_rule(M, N);
+    int rb = rule.rb;
+    if (const int f = opt().skinny_rb; f && mt <= 2) rb = f;
+    const int64_t blocks = (N + 16 * rb - 1) / (16 * rb), steps = K / 64;
+    int ks = stream_ks(rule, blocks, steps, stream_batch(mt, rb));
+    if (const int f = opt().skinny_ks; f > 0) {            // PQ_SKINNY_KS (experiments): a forced power of two, clamped to what the K-steps allow
+        ks = 1;
+        while (ks < f && ks < 16 && steps / (ks * 2) >= 1) ks <<= 1;
+    }
+    *rb_out = rb; *ks_out = ks;
+}
+
+// the grouped kernel: (MT, RB, KS).  MT follows M_total (1, 2 or 4 token tiles).  RB and KS: the same rule with the AVERAGE rows of a slot in place of M and blocks x slots
+// in place of the blocks of one matrix.  Its constants — ~4096 / 2048 / 768 waves per launch, the N thresholds — were swept for ONE dense N x K matrix; for a grid whose
+// slots may be empty and whose live experts lie E * N * K bytes apart they are UNMEASURED.
+// PQ_GROUPED_STREAM_RB / PQ_GROUPED_STREAM_KS force either (time only, never bits: tests/test_gpu_grouped_stream.py).
+void grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t K, int* mt_out, int* rb_out, int* ks_out) {
+    const int mt = M_total <= 16 ? 1 : (M_total <= 32 ? 2 : 4);
+    const int64_t slots = M_total < E ? (M_total < 1 ? 1 : M_total) : E;
+    const int64_t avg = M_total < 1 ? 1 : (M_total + slots - 1) / slots;
+    const StreamRule rule = stream_rule(avg, N);
+    int rb = rule.rb;
+    if (const int f = opt().grouped_stream_rb; f) rb = f;
+    if (mt > 2) rb = 1;                                    // (no two-block body for three or four token tiles)
+    const int64_t blocks = (N + 16 * rb - 1) / (16 * rb) * slots, steps = K / 64;
+    int ks = stream_ks(rule, blocks, steps, stream_batch((int)((avg + 15) / 16), rb));
+    if (const int f = opt().grouped_stream_ks; f > 0) {    // a forced power of two (<= 16), whatever K: waves without a k-step add zeros
+        ks = 1;
+        while (ks < f && ks < 16) ks <<= 1;
+    }
+    *mt_out = mt; *rb_out = rb; *ks_out = ks;
+}
+
 // ---- the names the query entry points report
+// static name of a grouped streaming plan: "gstream_mt<MT>_rb<RB>_ks<KS>_16x16x64"
+const char* grouped_stream_plan_name(int mt, int rb, int ks) {
+    static const struct Names {
+        char s[3][2][5][40];
+        Names() {
+            const int mts[3] = {1, 2, 4};
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 2; ++b)
+                    for (int k = 0; k < 5; ++k) snprintf(s[a][b][k], sizeof(s[a][b][k]), "gstream_mt%d_rb%d_ks%d_16x16x64", mts[a], b + 1, 1 << k);
+        }
+    } names;
+    int k = 0;
+    while ((1 << k) < ks && k < 4) ++k;
+    return names.s[mt == 1 ? 0 : (mt == 2 ? 1 : 2)][rb == 2 ? 1 : 0][k];
+}
+
 const char* gemm_variant_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
     // alignment of the pointers is unknown here: assume 16-byte aligned bases
     const Variant v = pick_variant(reinterpret_cast<const int8_t*>(16), lda, reinterpret_cast<const int8_t*>(16), ldb, M, N, K);

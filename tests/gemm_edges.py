@@ -209,12 +209,12 @@ def token_tiles(M):
     return (M + 15) // 16
 
 
-# COVERAGE BOOKKEEPING ONLY — a restatement of protoquant_amd/csrc/gemm_s8_skinny.hip, never a source of expected values:
-#   sk_batch      line 19          k-steps per batch
-#   skinny_plan   lines 224 - 243  (RB, KS) of a launch, PQ_SKINNY_RB / PQ_SKINNY_KS
-#   staged        line 253         const bool stage = opt().skinny_stage && M > 1
-#   skinny_walk   line 40 (a wave's slice s0 .. s1 of the K / 64 steps), lines 106 - 143 (whole batches; RB == 1: the two-register-set loop whose exits depend on the
-#                 parity of the batch count), lines 144 - 154 (the step-by-step tail)
+# COVERAGE BOOKKEEPING ONLY — a restatement of the dense weight-streaming kernel under protoquant_amd/csrc, never a source of expected values:
+#   sk_batch      gemm_stream_body.h: stream_batch, k-steps per batch
+#   skinny_plan   pq_plan.hip: stream_rule / stream_ks / skinny_plan, (RB, KS) of a launch, PQ_SKINNY_RB / PQ_SKINNY_KS
+#   staged        gemm_s8_skinny.hip: const bool stage = opt().skinny_stage && M > 1
+#   skinny_walk   gemm_stream_body.h: stream_body — a wave's slice s0 .. s1 of the K / 64 steps, the whole batches (RB == 1: the two-register-set loop whose exits depend
+#                 on the parity of the batch count), the step-by-step tail
 def sk_batch(mt, rb):
     return (4 if mt == 1 else 2) if rb == 1 else (4 if mt * rb == 2 else 2)
 

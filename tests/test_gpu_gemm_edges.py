@@ -323,3 +323,16 @@ def test_streaming_kernel_store_edges(pq, pq_opt, mt, rb):
                 r.launch(dp, E.BF16_B, M, N, mode=mode, shift="w")
         r.flush(mode)
     print(f"[gemm-edges] part 3 store edges mt={mt} rb={rb!r}: {r.launches} launches")
+
+
+def test_streaming_kernel_column_first_flags(pq):
+    """pq_qlinear_s8_t with more tokens than its EPI_STORE_T form takes and few output features: the swapped problem (the features as rows) is the planner's own choice
+    for the weight-streaming kernel, with EPI_COL_FIRST and, with a bias, EPI_BIAS_ROWS (EPI_STORE_T: test_streaming_kernel_store_edges)"""
+    p = E.problem(300, 40, E.K_EDGE, "full")
+    r = Runner(pq, "skinny, swapped problem", "tile", E.DISPLAY["skinny"], [p], 300, 300)
+    for kind in (E.BF16_BT, E.BF16_BT._replace(name="bf16^T without bias", bias=False)):
+        for M, N in ((300, 16), (129, 9), (65, 1)):          # (N <= 16: a swapped problem of one token tile goes to the streaming kernel whatever its width)
+            for mode in E.MODES:
+                r.launch(r.placed[0], kind, M, N, mode=mode)
+    r.flush()
+    print(f"[gemm-edges] part 3 column-first flags: {r.launches} launches")

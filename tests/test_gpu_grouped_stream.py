@@ -323,6 +323,40 @@ def test_forced_plans_give_the_same_bits(pq_opt, counts):
                 _same(_stream(pq, p), base, f"KS {ks} RB {rb} {kind} counts {counts}")
 
 
+# ---------------------------------------------------------------- the two hosts of the one weight-streaming body (gemm_stream_body.h)
+# K under ONE wave per workgroup picks the walk.  Both entries take multiples of 128 only, so with the 4-step batch (one token tile, RB = 1: 256 bytes of K) K = 128 is the
+# tail alone, 256 one batch, 384 a batch and a tail, 512 two batches (the pipelined loop leaves at its second check), 768 three (it leaves at the first check of its second
+# turn).  The 2-step bodies (128 bytes of K) see 1, 2, 3, 4 and 6 whole batches there — both exits of the pipelined loop, never a tail; their tails come from the uneven
+# slices of 18 k-steps under 4 and 16 waves in test_forced_plans_give_the_same_bits.
+WALK_K = (128, 256, 384, 512, 768)
+
+
+@pytest.mark.parametrize("rows", (1, 2, 16, 17, 33, 64))
+def test_every_walk_of_the_body_through_both_hosts(pq_opt, rows):
+    """E = 1, offsets = [0, rows], no row index: the grouped kernel and the dense kernel (forced, with the same RB and one wave per workgroup) run the same body on the same
+    operands and must agree exactly; the grouped result is held, as everywhere in this file, to qlinear_s8 per expert and to the 64-row tiles of qlinear_s8_grouped.
+    rows 1 .. 64: one to four token tiles, unstaged at one row only.  N = 40 and 100: ragged 16- and 32-row blocks, a scalar store tail; once an odd ldy."""
+    import protoquant_amd as pq
+    pq_opt("PQ_FORCE_VARIANT", "skinny")
+    for rb in ((1, 2) if rows <= 32 else (1,)):
+        pq_opt("PQ_GROUPED_STREAM_RB", rb); pq_opt("PQ_SKINNY_RB", rb)
+        for N in (40, 100):
+            for K in WALK_K + (("empty",) if N == 40 else ()):
+                ks = 1
+                if K == "empty":                                         # two k-steps under 16 forced waves: the grouped kernel runs fourteen waves with an empty
+                    K, ks = 128, 16                                      # slice, the dense planner clamps the forced split to the steps (two waves)
+                pq_opt("PQ_GROUPED_STREAM_KS", ks); pq_opt("PQ_SKINNY_KS", ks)
+                for kind in (torch.bfloat16, None):
+                    p = _operands(1000 * rows + K + N, [rows], N, K, kind, bias=True)
+                    what = f"rows {rows} RB {rb} N {N} K {K} KS {ks} {kind}"
+                    m = PLAN.match(_lib_name(1, rows, N, K))
+                    assert m and int(m.group(2)) == rb and int(m.group(3)) == ks, (what, m and m.groups())
+                    view = _check(pq, p, what, ldy=107 if (N == 100 and K == 384) else None)
+                    x, w = p["xq"].contiguous(), p["wq"][0].contiguous()
+                    dense = pq.int_mm(x, w) if kind is None else pq.qlinear_s8(x, p["xs"], w, p["ws"][0].contiguous(), p["bias"][0].contiguous(), kind)
+                    assert torch.equal(view, dense), f"{what}: the grouped and the dense host of one body differ"
+
+
 # ---------------------------------------------------------------- one captured launch, replayed over other routings
 def test_one_graph_replayed_over_three_routings():
     """a torch.cuda.graph capture of ONE streaming launch (a single chain: no side stream); between replays only the CONTENTS of offsets, row index, xs and the codes change"""

@@ -1,6 +1,7 @@
 """CPU: the host side of the grouped weight-streaming qlinear for decode (gemm_s8_grouped_stream.hip, pq_qlinear_s8_grouped_stream): exported symbols, argument validation
 before any HIP call, the (token tiles, RB, KS) planner and its two forcing switches, the Python wrappers' row limit, GroupedQLinear.stream_rows, and the built code object:
-every instantiation the launcher can reach is there, without scratch and without spills."""
+every instantiation the launcher can reach is there, without scratch and without spills.  Since the grouped and the dense streaming kernel share one body
+(gemm_stream_body.h) and one planner table: every plan of both against recorded ones, and the dense kernel's code object held the same way."""
 import os
 import re
 import subprocess
@@ -124,6 +125,59 @@ def test_plan_follows_the_two_forcing_switches():
     assert _plan(L, 8, 2, 4096, 14336) == _plan(L, 8, 2, 4096, 14336)
 
 
+# ---------------------------------------------------------------- both planners of the weight-streaming body against recorded plans
+# tests/golden/stream_plans.json: what the library returned for every point of the grid below BEFORE the two planners were written on one rule table in pq_plan.hip
+# (recorded results of this library; stream_plans() is what recorded them).  The dense planner has no C-ABI entry: pq::skinny_plan(M, N, K, &rb, &ks) is called through
+# its exported C++ symbol, outside a C-ABI call, where the planners read the live switches.
+PLAN_GOLDEN = os.path.join(ROOT, "tests", "golden", "stream_plans.json")
+PLAN_E, PLAN_M = (1, 8, 128, 1024), (1, 2, 8, 9, 16, 17, 32, 33, 64)
+PLAN_NK = LAYERS + ((4096, 4096), (4097, 4096), (16383, 4096), (16384, 4096), (4097, 256))
+PLAN_SWITCHES = {"grouped": ("",) + tuple(f"PQ_GROUPED_STREAM_{s}" for s in ("RB=1", "RB=2", "KS=1", "KS=4", "KS=16")),
+                 "dense": ("",) + tuple(f"PQ_SKINNY_{s}" for s in ("RB=1", "RB=2", "KS=1", "KS=4", "KS=16"))}
+
+
+def stream_plans(_l, L):
+    """{"grouped" | "dense": {switch setting: [plan of every grid point, E (grouped only) x M x (N, K) in that order]}}"""
+    import ctypes
+    skinny_plan = ctypes.CDLL(_l.LIB_PATH)._ZN2pq11skinny_planElllPiS0_
+    skinny_plan.restype, skinny_plan.argtypes = None, [ctypes.c_int64] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
+
+    def dense(M, N, K):
+        rb, ks = ctypes.c_int(0), ctypes.c_int(0)
+        skinny_plan(M, N, K, ctypes.byref(rb), ctypes.byref(ks))
+        return f"rb{rb.value}_ks{ks.value}"
+    out = {"grouped": {}, "dense": {}}
+    for side, settings in PLAN_SWITCHES.items():
+        for setting in settings:
+            name, _, value = setting.partition("=")
+            try:
+                if name:
+                    _l.set_option(name, value)
+                if side == "grouped":
+                    out[side][setting] = [L.pq_grouped_stream_plan_name(E, M, N, K).decode() for E in PLAN_E for M in PLAN_M for N, K in PLAN_NK]
+                else:
+                    out[side][setting] = [dense(M, N, K) for M in PLAN_M for N, K in PLAN_NK]
+            finally:
+                if name:
+                    _l.set_option(name, None)
+    return out
+
+
+def test_every_plan_of_both_streaming_kernels_is_the_recorded_one():
+    import json
+    _l, L = _lib()
+    want, got = json.load(open(PLAN_GOLDEN)), stream_plans(_l, L)
+    assert set(want) == set(got) == {"grouped", "dense"}
+    for side, settings in PLAN_SWITCHES.items():
+        assert set(want[side]) == set(settings)
+        points = [(E, M, N, K) for E in (PLAN_E if side == "grouped" else (None,)) for M in PLAN_M for N, K in PLAN_NK]
+        for setting in settings:
+            assert len(want[side][setting]) == len(got[side][setting]) == len(points)
+            bad = [(p, w, g) for p, w, g in zip(points, want[side][setting], got[side][setting]) if w != g]
+            assert not bad, f"{side} {setting!r}: {len(bad)} plans moved, first (E, M, N, K) = {bad[0][0]}: recorded {bad[0][1]}, now {bad[0][2]}"
+    assert len({p for s in want["grouped"].values() for p in s}) > 20 and len({p for s in want["dense"].values() for p in s}) >= 8, "the grid moves the plans"
+
+
 def test_wrappers_refuse_more_than_64_rows_before_the_library(monkeypatch):
     """the Python entry points check the row limit themselves (CPU tensors: require_gpu answers first, so the limit is checked through the shared helper)"""
     import importlib
@@ -177,6 +231,18 @@ def test_code_object_holds_every_reachable_instantiation_without_scratch_or_spil
     kernels = _kernel_notes()
     want = {f"Li{o}ELi{mt}ELi{rb}E" for o in range(4) for mt, rb in ((1, 1), (1, 2), (2, 1), (2, 2), (4, 1))}
     got = {re.search(r"gemm_s8_grouped_streamI((?:Li\d+E){3})E", k).group(1) for k in kernels}           # the mangled template arguments <OUT, MT, RB>
+    assert got == want, f"missing {sorted(want - got)}, unexpected {sorted(got - want)}"
+    for k, v in kernels.items():
+        assert v.get("private_segment_fixed_size") == 0 and v.get("vgpr_spill_count") == 0 and v.get("sgpr_spill_count") == 0, (k, v)
+        assert 0 < v.get("vgpr_count") <= 128, (k, v)
+
+
+def test_dense_host_of_the_body_holds_every_instantiation_without_scratch_or_spills():
+    """gemm_s8_skinny, the other host of gemm_stream_body.h: OUT in (bf16, fp16, f32, int32) x (MT, RB) in ((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (4, 1)) x STAGE —
+    what launch_gemm_skinny dispatches to.  Up to 16 waves per workgroup: at most 128 VGPRs."""
+    kernels = {k: v for k, v in kernels_of("gemm_s8_skinny").items() if "gemm_s8_skinny" in k}
+    want = {f"Li{o}ELi{mt}ELi{rb}ELb{st}E" for o in range(4) for mt, rb in ((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (4, 1)) for st in (0, 1)}
+    got = {re.search(r"gemm_s8_skinnyI((?:Li\d+E){3}Lb[01]E)E", k).group(1) for k in kernels}            # the mangled template arguments <OUT, MT, RB, STAGE>
     assert got == want, f"missing {sorted(want - got)}, unexpected {sorted(got - want)}"
     for k, v in kernels.items():
         assert v.get("private_segment_fixed_size") == 0 and v.get("vgpr_spill_count") == 0 and v.get("sgpr_spill_count") == 0, (k, v)
