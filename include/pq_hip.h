@@ -463,6 +463,29 @@ int32_t pq_gemm_s8s8s32_grouped_stream(const int8_t* xq, int64_t ldx, const int3
 /* "gstream_mt<1|2|4>_rb<1|2>_ks<1..16>_16x16x64": token tiles the kernel is compiled for, weight blocks per wave and waves per workgroup of that launch (static string). */
 const char* pq_grouped_stream_plan_name(int32_t E, int64_t M_total, int64_t N, int64_t K);
 
+/* INT4 WEIGHTS, format "W4 v1" (QSPEC W1-W4; w4_pack_kernels.hip, gemm_w4_stream.hip): a second, INTEGER quantisation level on top of the
+ * per-channel int8 weight wq s8[N, K], ws f32[N] (K2's output, unchanged).  Kp = K rounded up to a multiple of 128, tail codes 0; for row n and group j (k = 128 j ..
+ * 128 j + 127):  a = max |wq|,  g = min(18, max(1, ceil(a / 7))),  q = clamp(sign(w) * ((2 |w| + g) div (2 g)), -7, 7)  — so |q g| <= 126 and |q g - w| <= g div 2.
+ *   w4  u8[N][ldw4 >= Kp / 2]:  byte 64 j + i (i in 0 .. 63) of row n = q[n][128 j + i] in the low nibble, q[n][128 j + 64 + i] in the high one (two's complement).
+ *                               Nibble 0x8 is reserved: the packer never writes it, no entry validates it, and a kernel reads it as q = -8 (no address depends on it).
+ *   gs  u8[ceil(N / 4)][Kp / 128][4]:  byte ((n >> 2) * (Kp / 128) + j) * 4 + (n & 3) = g[n][j]; rows past N hold 1.
+ * The weight these stand for is the ordinary int8 matrix W8[n][k] = q[n][k] * g[n][k / 128], and the GEMM on them is DEFINED as pq_qlinear_s8 on W8: the same bits for
+ * every output dtype, with and without bias, whatever the plan — every sum is an exact integer.
+ * pq_w4_pack: wq (pitch ldw >= K) -> w4, gs; one wave per (row, group).  pq_w4_expand: w4, gs -> W8 s8[N, Kp] (pitch ldw8 >= Kp, a multiple of 16; 16-byte aligned):
+ * the format's definition in code and the prefill path.  pq_qlinear_w4: the decode GEMM, M <= 64 rows of int8 codes xq[M, Kp] (pitch ldx >= Kp, a multiple of 16; 16-byte
+ * aligned) with their scales xs[M], ONE launch of the weight-streaming int4 kernel: ceil(N / 16) workgroups of KS waves that split the Kp / 128 groups, each lane's
+ * 16-byte load holding its MFMA fragments of two k-steps; no workspace, no atomics, graph-capturable.  out_dtype: a PQ_* code; pq_gemm_s8w4s32 stores the int32 accumulator.
+ * PQ_SKINNY_KS forces KS (a power of two <= 16; waves without a group add zeros) — time only, never bits: tests/test_gpu_w4.py.
+ * Refused with PQ_ERR_BAD_ARG before any HIP call, pq_last_error naming the argument: M > 64, Kp not a positive multiple of 128, ldw4 < Kp / 2 or not a multiple of 16,
+ * ldx / ldw8 below Kp or not a multiple of 16, ldw < K, ldy < N, a null operand (bias excepted), w4 / xq / w8 not 16-byte aligned, gs not 4-byte aligned.  M == 0 or
+ * N == 0: nothing is read or written, returns PQ_OK. */
+int32_t pq_w4_pack(const void* wq, int64_t ldw, int64_t N, int64_t K, void* w4, int64_t ldw4, void* gs, void* stream);
+int32_t pq_w4_expand(const void* w4, int64_t ldw4, const void* gs, int64_t N, int64_t Kp, void* w8, int64_t ldw8, void* stream);
+int32_t pq_qlinear_w4(const void* xq, int64_t ldx, const float* xs, const void* w4, int64_t ldw4, const void* gs, const float* ws,
+                      const void* bias, void* y, int64_t ldy, int32_t out_dtype, int64_t M, int64_t N, int64_t Kp, void* stream);
+int32_t pq_gemm_s8w4s32(const void* xq, int64_t ldx, const void* w4, int64_t ldw4, const void* gs, void* acc, int64_t ldacc,
+                        int64_t M, int64_t N, int64_t Kp, void* stream);
+
 /* ROUTING of a mixture-of-experts layer (moe_kernels.hip, kernel R): the (token, slot) pairs of topk_ids[T, k] sorted by expert — a STABLE counting sort of the flat pairs
  * p = t * k + j by topk_ids[t][j].  All outputs int32, in device memory:
  *   offsets[E + 1]   rows offsets[e] .. offsets[e + 1] - 1 of the grouped order belong to expert e (what pq_qlinear_s8_grouped takes as offsets)

@@ -89,6 +89,10 @@ SIGNATURES = {
     "pq_hadamard_quant_rows": (i32, [vp, i32, i64, i64, i64, i32, vp, i64, vp, vp, i64, vp]),
     "pq_gated_hadamard_quant_rows": (i32, [vp, i64, vp, i64, i32, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp]),
     "pq_moe_topk": (i32, [vp, i32, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, i32, i64, vp]),
+    "pq_w4_pack": (i32, [vp, i64, i64, i64, vp, i64, vp, vp]),
+    "pq_w4_expand": (i32, [vp, i64, vp, i64, i64, vp, i64, vp]),
+    "pq_qlinear_w4": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, i32, i64, i64, i64, vp]),
+    "pq_gemm_s8w4s32": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1110,6 +1110,81 @@ const char* pq_grouped_stream_plan_name(int32_t E, int64_t M_total, int64_t N, i
     return pq::grouped_stream_plan_name(mt, rb, ks);
 }
 
+// ---- int4 weights (QSPEC W1-W4): the packer, the expansion (the format's definition and the prefill path) and the decode GEMM on the packed weight.  Every argument
+// is checked, and the failing one named, before any HIP call.
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the packed operand of every W4 entry: N rows of Kp / 2 bytes at pitch ldw4, ceil(N / 4) * (Kp / 128) dwords of multipliers
+static int32_t w4_operand_check(const char* what, const void* w4, int64_t ldw4, const void* gs, int64_t N, int64_t Kp) {
+    if (N < 0 || N >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: N = %lld", what, (long long)N);
+    if (Kp < 128 || Kp % 128 != 0 || Kp >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: Kp = %lld must be a positive multiple of 128 (the packed tail holds zeros)", what, (long long)Kp);
+    if ((N + 3) / 4 * (Kp / 128) >= ((int64_t)1 << 30)) return fail(PQ_ERR_BAD_ARG, "%s: N * Kp / 512 = %lld groups of multipliers (< 2^30)", what, (long long)((N + 3) / 4 * (Kp / 128)));
+    if (ldw4 < Kp / 2 || ldw4 % 16 != 0) return fail(PQ_ERR_BAD_ARG, "%s: ldw4 = %lld (>= Kp / 2 = %lld bytes, a multiple of 16)", what, (long long)ldw4, (long long)(Kp / 2));
+    if (N > 0 && (!w4 || !gs)) return fail(PQ_ERR_BAD_ARG, "%s: %s is null", what, !w4 ? "w4" : "gs");
+    if (!al16(w4)) return fail(PQ_ERR_BAD_ARG, "%s: w4 must be 16-byte aligned", what);
+    if ((reinterpret_cast<uintptr_t>(gs) & 3) != 0) return fail(PQ_ERR_BAD_ARG, "%s: gs must be 4-byte aligned", what);
+    return PQ_OK;
+}
+
+int32_t pq_w4_pack(const void* wq, int64_t ldw, int64_t N, int64_t K, void* w4, int64_t ldw4, void* gs, void* stream) {
+    Range range_("pq:w4_pack");
+    if (K < 1 || K >= ((int64_t)1 << 30) - 128) return fail(PQ_ERR_BAD_ARG, "pq_w4_pack: K = %lld", (long long)K);
+    if (const int32_t rc = w4_operand_check("pq_w4_pack", w4, ldw4, gs, N, (K + 127) / 128 * 128)) return rc;
+    if (ldw < K) return fail(PQ_ERR_BAD_ARG, "pq_w4_pack: ldw = %lld < K = %lld", (long long)ldw, (long long)K);
+    if (N == 0) return PQ_OK;
+    if (!wq) return fail(PQ_ERR_BAD_ARG, "pq_w4_pack: wq is null");
+    pq::launch_w4_pack(static_cast<const int8_t*>(wq), ldw, N, K, static_cast<uint8_t*>(w4), ldw4, static_cast<uint8_t*>(gs), static_cast<hipStream_t>(stream));
+    return check_launch("pq_w4_pack");
+}
+
+int32_t pq_w4_expand(const void* w4, int64_t ldw4, const void* gs, int64_t N, int64_t Kp, void* w8, int64_t ldw8, void* stream) {
+    Range range_("pq:w4_expand");
+    if (const int32_t rc = w4_operand_check("pq_w4_expand", w4, ldw4, gs, N, Kp)) return rc;
+    if (ldw8 < Kp || ldw8 % 16 != 0) return fail(PQ_ERR_BAD_ARG, "pq_w4_expand: ldw8 = %lld (>= Kp, a multiple of 16)", (long long)ldw8);
+    if (N == 0) return PQ_OK;
+    if (!w8) return fail(PQ_ERR_BAD_ARG, "pq_w4_expand: w8 is null");
+    if (!al16(w8)) return fail(PQ_ERR_BAD_ARG, "pq_w4_expand: w8 must be 16-byte aligned");
+    pq::launch_w4_expand(static_cast<const uint8_t*>(w4), ldw4, static_cast<const uint8_t*>(gs), N, Kp, static_cast<int8_t*>(w8), ldw8, static_cast<hipStream_t>(stream));
+    return check_launch("pq_w4_expand");
+}
+
+// everything pq_qlinear_w4 and pq_gemm_s8w4s32 have in common; *empty: nothing to launch
+static int32_t w4_gemm_check(const char* what, const void* xq, int64_t ldx, const void* w4, int64_t ldw4, const void* gs, const void* y, int64_t ldy, int64_t M, int64_t N,
+                             int64_t Kp, bool* empty) {
+    *empty = false;
+    if (M < 0) return fail(PQ_ERR_BAD_ARG, "%s: M = %lld", what, (long long)M);
+    if (M > 64) return fail(PQ_ERR_BAD_ARG, "%s: M = %lld (the weight-streaming int4 kernel serves at most 64 rows; pq_w4_expand and pq_qlinear_s8 serve any number)", what, (long long)M);
+    if (const int32_t rc = w4_operand_check(what, w4, ldw4, gs, N, Kp)) return rc;
+    if (ldx < Kp || ldx % 16 != 0) return fail(PQ_ERR_BAD_ARG, "%s: ldx = %lld (>= Kp, a multiple of 16)", what, (long long)ldx);
+    if (ldy < N) return fail(PQ_ERR_BAD_ARG, "%s: ldy = %lld < N = %lld", what, (long long)ldy, (long long)N);
+    if (M == 0 || N == 0) { *empty = true; return PQ_OK; }
+    if (!xq || !y) return fail(PQ_ERR_BAD_ARG, "%s: %s is null", what, !xq ? "xq" : "y");
+    if (!al16(xq)) return fail(PQ_ERR_BAD_ARG, "%s: xq must be 16-byte aligned", what);
+    return PQ_OK;
+}
+
+int32_t pq_qlinear_w4(const void* xq, int64_t ldx, const float* xs, const void* w4, int64_t ldw4, const void* gs, const float* ws, const void* bias, void* y, int64_t ldy,
+                      int32_t out_dtype, int64_t M, int64_t N, int64_t Kp, void* stream) {
+    Range range_("pq:qlinear_w4 (K3+K4)");
+    if (const int32_t rc = check_dtype("pq_qlinear_w4", out_dtype)) return rc;
+    bool empty;
+    if (const int32_t rc = w4_gemm_check("pq_qlinear_w4", xq, ldx, w4, ldw4, gs, y, ldy, M, N, Kp, &empty); rc || empty) return rc;
+    if (!xs || !ws) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_w4: %s is null", !xs ? "xs" : "ws");
+    const pq::EpiArgs epi = make_epi(xs, ws, bias, y, ldy, 0, EPI_BARE);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(out_dtype, [&](auto dt) { pq::launch_gemm_w4_stream<dt>(static_cast<const int8_t*>(xq), ldx, static_cast<const uint8_t*>(w4), ldw4, static_cast<const uint8_t*>(gs), epi, M, N, Kp, st); });
+    return check_launch("pq_qlinear_w4");
+}
+
+int32_t pq_gemm_s8w4s32(const void* xq, int64_t ldx, const void* w4, int64_t ldw4, const void* gs, void* acc, int64_t ldacc, int64_t M, int64_t N, int64_t Kp, void* stream) {
+    Range range_("pq:gemm_s8w4s32 (K3)");
+    bool empty;
+    if (const int32_t rc = w4_gemm_check("pq_gemm_s8w4s32", xq, ldx, w4, ldw4, gs, acc, ldacc, M, N, Kp, &empty); rc || empty) return rc;
+    const pq::EpiArgs epi = make_epi(nullptr, nullptr, nullptr, acc, ldacc, 0, EPI_BARE);
+    pq::launch_gemm_w4_stream<pq::OUT_I32>(static_cast<const int8_t*>(xq), ldx, static_cast<const uint8_t*>(w4), ldw4, static_cast<const uint8_t*>(gs), epi, M, N, Kp,
+                                           static_cast<hipStream_t>(stream));
+    return check_launch("pq_gemm_s8w4s32");
+}
+
 // ---- routing and combine of a mixture-of-experts layer (moe_kernels.hip): every argument is checked, and the failing one named, before any HIP call
 static int32_t moe_dims_check(const char* what, int64_t T, int32_t k, int32_t E, bool with_E) {
     if (with_E && (E <= 0 || E > 1024)) return fail(PQ_ERR_BAD_ARG, "%s: E = %d (1 .. 1024 experts)", what, E);

@@ -24,6 +24,10 @@ int grouped_plan(int32_t E, int64_t M_total, int64_t N);
 void skinny_plan(int64_t M, int64_t N, int64_t K, int* rb_out, int* ks_out);
 void grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t K, int* mt_out, int* rb_out, int* ks_out);
 const char* grouped_stream_plan_name(int mt, int rb, int ks);
+// the int4 weight-streaming kernel (gemm_w4_stream.hip): groups (128 k, 64 packed bytes per row) per batch of a wave with nt token tiles, sized like stream_batch — the
+// staging regions of 16 waves stay within 160 KiB of LDS — and its K split: the same rule table over steps = Kp / 128 groups, one block per wave
+constexpr int w4_stream_batch(int nt) { return nt == 1 ? 4 : (nt == 2 ? 2 : 1); }
+void w4_stream_plan(int64_t M, int64_t N, int64_t Kp, int* ks_out);
 
 // what pq_gemm_variant_name, pq_kslabs_way_name and pq_grouped_variant_name return (the caller has pinned the snapshot)
 const char* gemm_variant_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb);

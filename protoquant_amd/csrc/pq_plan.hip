@@ -248,6 +248,18 @@ void skinny_plan(int64_t M, int64_t N, int64_t K, int* rb_out, int* ks_out) {
     *rb_out = rb; *ks_out = ks;
 }
 
+// the int4 kernel: the rule of its M tokens with the Kp / 128 groups as the steps and always one block per wave (the rule's RB is not read: its thresholds were swept
+// for int8 rows and are UNMEASURED for packed ones).  PQ_SKINNY_KS forces the split — a power of two (<= 16) whatever Kp: waves without a group add zeros.
+void w4_stream_plan(int64_t M, int64_t N, int64_t Kp, int* ks_out) {
+    const StreamRule rule = stream_rule(M, N);
+    int ks = stream_ks(rule, (N + 15) / 16, Kp / 128, w4_stream_batch((int)((M + 15) / 16)));
+    if (const int f = opt().skinny_ks; f > 0) {
+        ks = 1;
+        while (ks < f && ks < 16) ks <<= 1;
+    }
+    *ks_out = ks;
+}
+
 // the grouped kernel: (MT, RB, KS).  MT follows M_total (1, 2 or 4 token tiles).  RB and KS: the same rule with the AVERAGE rows of a slot in place of M and blocks x slots
 // in place of the blocks of one matrix.  Its constants — ~4096 / 2048 / 768 waves per launch, the N thresholds — were swept for ONE dense N x K matrix; for a grid whose
 // slots may be empty and whose live experts lie E * N * K bytes apart they are UNMEASURED.
