@@ -485,6 +485,30 @@ int32_t pq_qlinear_w4(const void* xq, int64_t ldx, const float* xs, const void* 
                       const void* bias, void* y, int64_t ldy, int32_t out_dtype, int64_t M, int64_t N, int64_t Kp, void* stream);
 int32_t pq_gemm_s8w4s32(const void* xq, int64_t ldx, const void* w4, int64_t ldw4, const void* gs, void* acc, int64_t ldacc,
                         int64_t M, int64_t N, int64_t Kp, void* stream);
+/* INT4 EXPERT WEIGHTS AT DECODE (gemm_w4_grouped_stream.hip): the contract of pq_qlinear_s8_grouped_stream — rows sorted by expert, offsets[E + 1] and the nullable
+ * a_row_index in device memory and never read on the host, xs in grouped order, M_total <= 64 — on E stacked W4 v1 operands (the format version does not change):
+ *   w4  u8[E][N][ldw4 >= Kp / 2], expert e at w4 + e * w4_expert_stride (bytes; a multiple of 16, >= (N - 1) * ldw4 + Kp / 2); base 16-byte aligned, ldw4 a multiple of 16;
+ *   gs  u8[E][ceil(N / 4)][Kp / 128][4], expert e at gs + e * gs_expert_stride (bytes; a multiple of 4, >= ceil(N / 4) * (Kp / 128) * 4): PER EXPERT the layout above,
+ *       rows past N hold 1 — expert e's slice is what pq_w4_pack gives for wq[e];
+ *   ws  f32[E][N];  bias [E][N] in the output dtype, nullable.
+ * y[r, :] = dequant(xq[src(r), :] . W8[e(r)]^T) with W8[e] = pq_w4_expand(w4[e], gs[e]): every result is bit for bit what pq_qlinear_s8_grouped_stream gives on the
+ * expanded [E, N, Kp] weight; rows >= offsets[E] of y are not written; offsets and indices are clamped as there.  ONE launch: ceil(N / 16) weight blocks x min(E, M_total)
+ * expert slots, KS waves per workgroup split the Kp / 128 groups of one 16-row block of one live expert (Kp / 2 + Kp / 128 bytes per weight row), an expert's body is
+ * chosen on the device from ITS row count.  No workspace, no atomics, no wait between workgroups; graph-capturable, a replay is right when only the contents of
+ * offsets / a_row_index / xs change.  pq_gemm_s8w4s32_grouped_stream stores the exact int32 accumulators.
+ * PQ_GROUPED_STREAM_KS forces KS (a power of two <= 16; waves without a group add zeros) — time only, never bits: tests/test_gpu_w4_grouped.py; PQ_GROUPED_STREAM_RB is
+ * ignored (one weight block per wave).
+ * Refused with PQ_ERR_BAD_ARG before any HIP call, pq_last_error naming the argument: E outside 1 .. 1024, M_total > 64, Kp not a positive multiple of 128, ldw4 < Kp / 2
+ * or not a multiple of 16, a bad w4_expert_stride / gs_expert_stride, ldx below Kp or not a multiple of 16, ldy < N, x_rows < M_total without a_row_index, a null operand
+ * (bias and a_row_index excepted), w4 / xq not 16-byte aligned, gs not 4-byte aligned.  M_total == 0 or N == 0: nothing is read or written, returns PQ_OK. */
+int32_t pq_qlinear_w4_grouped_stream(const void* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs,
+                                     const void* w4, int64_t ldw4, int64_t w4_expert_stride, const void* gs, int64_t gs_expert_stride,
+                                     const float* ws, const void* bias, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t Kp,
+                                     void* y, int64_t ldy, int32_t out_dtype, void* stream);
+int32_t pq_gemm_s8w4s32_grouped_stream(const void* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows,
+                                       const void* w4, int64_t ldw4, int64_t w4_expert_stride, const void* gs, int64_t gs_expert_stride,
+                                       const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t Kp,
+                                       int32_t* acc, int64_t ldacc, void* stream);
 
 /* ROUTING of a mixture-of-experts layer (moe_kernels.hip, kernel R): the (token, slot) pairs of topk_ids[T, k] sorted by expert — a STABLE counting sort of the flat pairs
  * p = t * k + j by topk_ids[t][j].  All outputs int32, in device memory:

@@ -11,7 +11,7 @@ from .gemma import GemmaRMSNormQuant, GemmaSandwichNormQuant, SandwichFusedLayer
 from .olmo import OlmoRMSNorm, PostNormFusedLayer, fuse_olmo_layers, is_olmo_rmsnorm, residual_flow_is_postnorm
 from .qk_norm import HeadRMSNorm, fuse_qk_norms, head_norm_kind
 from .hadamard import RotatedQLinear, gated_hadamard_quantize, hadamard, hadamard_quantize, rotate_gated_mlps, rotate_linears
-from .w4 import QLinearW4, int_mm_w4, qlinear_w4, swap_linears_w4, w4_expand, w4_pack
+from .w4 import GroupedQLinearW4, QLinearW4, int_mm_w4, int_mm_w4_grouped, qlinear_w4, qlinear_w4_grouped, swap_linears_w4, swap_moe_experts_w4, w4_expand, w4_pack
 from .granite import ScaledResidualFusedLayer, fuse_granite_residual, residual_flow_is_scaled
 from .sharded import (ColumnShardedGatedMLP, ColumnShardedQLinear, RcclColumnGather, RcclRowReduceScatter, RowShardedQLinear, ShardedGatedMLP,
                       gather_columns, gather_columns_overlapped, gather_rows_t, reduce_rows, shard_bounds)
@@ -30,4 +30,5 @@ __all__ = ["QTensor", "quantize", "dequantize", "qlinear", "qlinear_s8", "qlinea
            "head_rmsnorm", "HeadRMSNorm", "fuse_qk_norms", "head_norm_kind",
            "hadamard", "hadamard_quantize", "RotatedQLinear", "rotate_linears", "gated_hadamard_quantize", "rotate_gated_mlps",
            "moe_topk", "fuse_moe_routers", "router_parts", "RouterParts",
-           "w4_pack", "w4_expand", "qlinear_w4", "int_mm_w4", "QLinearW4", "swap_linears_w4"]
+           "w4_pack", "w4_expand", "qlinear_w4", "int_mm_w4", "QLinearW4", "swap_linears_w4",
+           "qlinear_w4_grouped", "int_mm_w4_grouped", "GroupedQLinearW4", "swap_moe_experts_w4"]

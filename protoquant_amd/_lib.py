@@ -93,6 +93,8 @@ SIGNATURES = {
     "pq_w4_expand": (i32, [vp, i64, vp, i64, i64, vp, i64, vp]),
     "pq_qlinear_w4": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, i32, i64, i64, i64, vp]),
     "pq_gemm_s8w4s32": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, vp]),
+    "pq_qlinear_w4_grouped_stream": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp, i32, i64, i64, i64, vp, i64, i32, vp]),
+    "pq_gemm_s8w4s32_grouped_stream": (i32, [vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, i32, i64, i64, i64, vp, i64, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1185,6 +1185,71 @@ int32_t pq_gemm_s8w4s32(const void* xq, int64_t ldx, const void* w4, int64_t ldw
     return check_launch("pq_gemm_s8w4s32");
 }
 
+// ---- int4 expert weights at decode (gemm_w4_grouped_stream.hip): the grouped contract of pq_qlinear_s8_grouped_stream on E stacked W4 operands.  Everything
+// pq_qlinear_w4_grouped_stream and pq_gemm_s8w4s32_grouped_stream have in common; no HIP call is made before the checks are through; *empty: nothing to launch
+static int32_t w4_grouped_check(const char* what, const void* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const void* w4, int64_t ldw4,
+                                int64_t w4_expert_stride, const void* gs, int64_t gs_expert_stride, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t Kp,
+                                const void* y, int64_t ldy, bool* empty) {
+    *empty = false;
+    if (E <= 0 || E > 1024) return fail(PQ_ERR_BAD_ARG, "%s: E = %d (1 .. 1024 experts)", what, E);
+    if (M_total < 0) return fail(PQ_ERR_BAD_ARG, "%s: M_total = %lld", what, (long long)M_total);
+    if (M_total > 64)
+        return fail(PQ_ERR_BAD_ARG, "%s: M_total = %lld (the weight-streaming grouped int4 kernel serves at most 64 grouped rows; pq_w4_expand and pq_qlinear_s8_grouped serve any number)",
+                    what, (long long)M_total);
+    if (const int32_t rc = w4_operand_check(what, w4, ldw4, gs, N, Kp)) return rc;
+    if (ldw4 >= (1 << 23)) return fail(PQ_ERR_BAD_ARG, "%s: ldw4 = %lld (< 2^23)", what, (long long)ldw4);
+    if (w4_expert_stride % 16 != 0 || (N > 0 && w4_expert_stride < (N - 1) * ldw4 + Kp / 2))
+        return fail(PQ_ERR_BAD_ARG, "%s: w4_expert_stride = %lld (a multiple of 16, >= (N - 1) * ldw4 + Kp / 2)", what, (long long)w4_expert_stride);
+    const int64_t gs_bytes = (N + 3) / 4 * (Kp / 128) * 4;
+    if (gs_expert_stride % 4 != 0 || gs_expert_stride < gs_bytes)
+        return fail(PQ_ERR_BAD_ARG, "%s: gs_expert_stride = %lld (a multiple of 4, >= ceil(N / 4) * (Kp / 128) * 4 = %lld)", what, (long long)gs_expert_stride, (long long)gs_bytes);
+    if (x_rows < 0 || x_rows >= ((int64_t)1 << 31)) return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld", what, (long long)x_rows);
+    if (ldx < Kp || ldx % 16 != 0 || ldx >= (1 << 23)) return fail(PQ_ERR_BAD_ARG, "%s: ldx = %lld (>= Kp, a multiple of 16, < 2^23)", what, (long long)ldx);
+    if (ldy < N) return fail(PQ_ERR_BAD_ARG, "%s: ldy = %lld < N = %lld", what, (long long)ldy, (long long)N);
+    if (!offsets) return fail(PQ_ERR_BAD_ARG, "%s: offsets is null", what);
+    if (a_row_index) {
+        if (x_rows < 1) return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld with a_row_index", what, (long long)x_rows);
+        if (x_rows * ldx >= ((int64_t)1 << 32)) return fail(PQ_ERR_BAD_ARG, "%s: x_rows * ldx = %lld >= 2^32 with a_row_index", what, (long long)(x_rows * ldx));
+    } else if (x_rows < M_total) {
+        return fail(PQ_ERR_BAD_ARG, "%s: x_rows = %lld < M_total = %lld without a_row_index", what, (long long)x_rows, (long long)M_total);
+    }
+    if (M_total == 0 || N == 0) { *empty = true; return PQ_OK; }
+    if (!xq || !y) return fail(PQ_ERR_BAD_ARG, "%s: %s is null", what, !xq ? "xq" : "y");
+    if (!al16(xq)) return fail(PQ_ERR_BAD_ARG, "%s: xq must be 16-byte aligned", what);
+    return PQ_OK;
+}
+
+int32_t pq_qlinear_w4_grouped_stream(const void* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const float* xs, const void* w4, int64_t ldw4,
+                                     int64_t w4_expert_stride, const void* gs, int64_t gs_expert_stride, const float* ws, const void* bias, const int32_t* offsets, int32_t E,
+                                     int64_t M_total, int64_t N, int64_t Kp, void* y, int64_t ldy, int32_t out_dtype, void* stream) {
+    Range range_("pq:qlinear_w4_grouped_stream (K3+K4)");
+    if (const int32_t rc = check_dtype("pq_qlinear_w4_grouped_stream", out_dtype)) return rc;
+    bool empty;
+    if (const int32_t rc = w4_grouped_check("pq_qlinear_w4_grouped_stream", xq, ldx, a_row_index, x_rows, w4, ldw4, w4_expert_stride, gs, gs_expert_stride, offsets, E, M_total,
+                                            N, Kp, y, ldy, &empty); rc || empty) return rc;
+    if (!xs || !ws) return fail(PQ_ERR_BAD_ARG, "pq_qlinear_w4_grouped_stream: %s is null", !xs ? "xs" : "ws");
+    const pq::EpiArgs epi = make_epi(xs, ws, bias, y, ldy, 0, EPI_BARE);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    by_dtype(out_dtype, [&](auto dt) {
+        pq::launch_gemm_w4_grouped_stream<dt>(static_cast<const int8_t*>(xq), ldx, a_row_index, x_rows, static_cast<const uint8_t*>(w4), ldw4, w4_expert_stride,
+                                              static_cast<const uint8_t*>(gs), gs_expert_stride, epi, offsets, E, M_total, N, Kp, st);
+    });
+    return check_launch("pq_qlinear_w4_grouped_stream");
+}
+
+int32_t pq_gemm_s8w4s32_grouped_stream(const void* xq, int64_t ldx, const int32_t* a_row_index, int64_t x_rows, const void* w4, int64_t ldw4, int64_t w4_expert_stride,
+                                       const void* gs, int64_t gs_expert_stride, const int32_t* offsets, int32_t E, int64_t M_total, int64_t N, int64_t Kp, int32_t* acc,
+                                       int64_t ldacc, void* stream) {
+    Range range_("pq:gemm_s8w4s32_grouped_stream (K3)");
+    bool empty;
+    if (const int32_t rc = w4_grouped_check("pq_gemm_s8w4s32_grouped_stream", xq, ldx, a_row_index, x_rows, w4, ldw4, w4_expert_stride, gs, gs_expert_stride, offsets, E,
+                                            M_total, N, Kp, acc, ldacc, &empty); rc || empty) return rc;
+    const pq::EpiArgs epi = make_epi(nullptr, nullptr, nullptr, acc, ldacc, 0, EPI_BARE);
+    pq::launch_gemm_w4_grouped_stream<pq::OUT_I32>(static_cast<const int8_t*>(xq), ldx, a_row_index, x_rows, static_cast<const uint8_t*>(w4), ldw4, w4_expert_stride,
+                                                   static_cast<const uint8_t*>(gs), gs_expert_stride, epi, offsets, E, M_total, N, Kp, static_cast<hipStream_t>(stream));
+    return check_launch("pq_gemm_s8w4s32_grouped_stream");
+}
+
 // ---- routing and combine of a mixture-of-experts layer (moe_kernels.hip): every argument is checked, and the failing one named, before any HIP call
 static int32_t moe_dims_check(const char* what, int64_t T, int32_t k, int32_t E, bool with_E) {
     if (with_E && (E <= 0 || E > 1024)) return fail(PQ_ERR_BAD_ARG, "%s: E = %d (1 .. 1024 experts)", what, E);

@@ -102,9 +102,13 @@ template <int DT> void moe_combine_dispatch(const void* y, int64_t ldy, int64_t 
 template <int DT> void moe_topk_dispatch(const void* logits, int64_t ld_logits, int64_t T, int E, int k, int kind, int renormalise, void* weights, int w_dtype, int64_t ld_w,
                                          void* ids, bool ids_are_int64, int64_t ld_ids, hipStream_t st);
 // ---- the int4 weight format (QSPEC W1-W4): w4_pack_kernels.hip (int8 codes -> nibbles + group multipliers, and back: the prefill path) and gemm_w4_stream.hip (the
-// weight-streaming decode GEMM on the packed weight, M <= 64; its K split is pq_plan.h's w4_stream_plan)
+// weight-streaming decode GEMM on the packed weight, M <= 64; its K split is pq_plan.h's w4_stream_plan) and gemm_w4_grouped_stream.hip (the same body over the live
+// experts of a mixture-of-experts layer, M_total <= 64 grouped rows; w4_stride and gs_stride in bytes; w4_grouped_stream_plan)
 void launch_w4_pack(const int8_t* wq, int64_t ldw, int64_t N, int64_t K, uint8_t* w4, int64_t ldw4, uint8_t* gs, hipStream_t st);
 void launch_w4_expand(const uint8_t* w4, int64_t ldw4, const uint8_t* gs, int64_t N, int64_t Kp, int8_t* w8, int64_t ldw8, hipStream_t st);
 template <int OUT> void launch_gemm_w4_stream(const int8_t* X, int64_t ldx, const uint8_t* W4, int64_t ldw4, const uint8_t* GS, const EpiArgs& epi, int64_t M, int64_t N,
                                               int64_t Kp, hipStream_t st);
+template <int OUT> void launch_gemm_w4_grouped_stream(const int8_t* X, int64_t ldx, const int32_t* qrow, int64_t x_rows, const uint8_t* W4, int64_t ldw4, int64_t w4_stride,
+                                                      const uint8_t* GS, int64_t gs_stride, const EpiArgs& epi, const int32_t* offsets, int E, int64_t M_total, int64_t N,
+                                                      int64_t Kp, hipStream_t st);
 }  // namespace pq

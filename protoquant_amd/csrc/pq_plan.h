@@ -28,6 +28,8 @@ const char* grouped_stream_plan_name(int mt, int rb, int ks);
 // staging regions of 16 waves stay within 160 KiB of LDS — and its K split: the same rule table over steps = Kp / 128 groups, one block per wave
 constexpr int w4_stream_batch(int nt) { return nt == 1 ? 4 : (nt == 2 ? 2 : 1); }
 void w4_stream_plan(int64_t M, int64_t N, int64_t Kp, int* ks_out);
+// ... and its grouped host (gemm_w4_grouped_stream.hip): MT token tiles from M_total, KS as grouped_stream_plan asks the table, over groups and one block per wave
+void w4_grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t Kp, int* mt_out, int* ks_out);
 
 // what pq_gemm_variant_name, pq_kslabs_way_name and pq_grouped_variant_name return (the caller has pinned the snapshot)
 const char* gemm_variant_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb);

@@ -281,6 +281,21 @@ void grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t K, int* 
     *mt_out = mt; *rb_out = rb; *ks_out = ks;
 }
 
+// the grouped int4 kernel: MT follows M_total as above; KS is the rule of the average rows of a slot over blocks x slots with the Kp / 128 groups as the steps, always
+// one block per wave (the rule's RB is not read, PQ_GROUPED_STREAM_RB is ignored).  The table was swept for int8 rows of ONE dense matrix: for packed rows, and for a
+// grid of expert slots, it is UNMEASURED.  PQ_GROUPED_STREAM_KS forces the split (time only, never bits: tests/test_gpu_w4_grouped.py).
+void w4_grouped_stream_plan(int32_t E, int64_t M_total, int64_t N, int64_t Kp, int* mt_out, int* ks_out) {
+    const int64_t slots = M_total < E ? (M_total < 1 ? 1 : M_total) : E;
+    const int64_t avg = M_total < 1 ? 1 : (M_total + slots - 1) / slots;
+    int ks = stream_ks(stream_rule(avg, N), (N + 15) / 16 * slots, Kp / 128, w4_stream_batch((int)((avg + 15) / 16)));
+    if (const int f = opt().grouped_stream_ks; f > 0) {    // a forced power of two (<= 16), whatever Kp: waves without a group add zeros
+        ks = 1;
+        while (ks < f && ks < 16) ks <<= 1;
+    }
+    *mt_out = M_total <= 16 ? 1 : (M_total <= 32 ? 2 : 4);
+    *ks_out = ks;
+}
+
 // ---- the names the query entry points report
 // static name of a grouped streaming plan: "gstream_mt<MT>_rb<RB>_ks<KS>_16x16x64"
 const char* grouped_stream_plan_name(int mt, int rb, int ks) {

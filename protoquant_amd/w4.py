@@ -10,18 +10,25 @@ and without bias, whatever the plan — so the format has an exact twin in the l
     int_mm_w4(xq, w4, gs)          the exact int32 accumulators of the streaming kernel (<= 64 rows)
     QLinearW4                      a qlinear that keeps w4 / gs instead of wq (half the weight memory)
     swap_linears_w4(model, ..)     opt-in: chosen nn.Linear -> QLinearW4; call it BEFORE swap_linears (which takes the remaining layers) and the fuse_* entries
+    qlinear_w4_grouped(..)         the experts of a mixture-of-experts layer, stacked: w4 u8[E, N, Kp / 2], gs u8[E, ceil(N / 4), Kp / 128, 4] (per expert what w4_pack
+                                   gives for wq[e]).  <= 64 grouped rows: ONE launch of the grouped weight-streaming int4 kernel over the live experts; more rows: all
+                                   experts expanded into the cached workspace, then qlinear_s8_grouped.  The bits of qlinear_s8_grouped on the expanded weight either way
+    int_mm_w4_grouped(..)          the exact int32 accumulators of the grouped streaming kernel (<= 64 grouped rows)
+    GroupedQLinearW4               a GroupedQLinear that keeps w4 / gs instead of wq; MoEGatedMLP runs unchanged with two of them
+    swap_moe_experts_w4(model, ..) opt-in: the GroupedQLinear pair of chosen MoEGatedMLP modules -> GroupedQLinearW4; call it AFTER swap_moe_experts
 
 The activation side is unchanged: dynamic per-token int8, the same codes.  The fuse_* entries read `.wq` of the linears they merge, so they leave a QLinearW4 and what
-would have fed it alone (qlinear.is_code_fed).  There is no CPU path.  Out of scope: a grouped (MoE) host and GroupedQLinear, FusedQLinear / GatedMLP over W4 weights, the
-sharded modules, serialize.py / convert_checkpoint (the module's state_dict is the persistent form), RotatedQLinear with W4 weights, zero points, other group sizes,
-calibration, float-activation weight-only GEMMs."""
+would have fed it alone (qlinear.is_code_fed).  There is no CPU path.  Out of scope: FusedQLinear / GatedMLP over W4 weights, the sharded modules, serialize.py /
+convert_checkpoint for packed weights, dense or expert (the modules' state_dict is the persistent form), MoEBlock-level changes, a grouped int4 PREFILL kernel (more than
+64 grouped rows expand and run the int8 tiles), RotatedQLinear with W4 weights, zero points, other group sizes, calibration, float-activation weight-only GEMMs."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
 from . import _lib as L
-from .qlinear import _check_operand, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8
+from .moe import GroupedQLinear, MoEGatedMLP
+from .qlinear import _check_operand, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8, qlinear_s8_grouped
 from .qtensor import QTensor, _launch, _on_gpu, _ptr
 
 GROUP = 128
@@ -226,4 +233,169 @@ def swap_linears_w4(model: nn.Module, predicate=None) -> int:
             n += 1
         else:
             n += swap_linears_w4(child, predicate)
+    return n
+
+
+# ---- the experts of a mixture-of-experts layer: E packed weights stacked, the grouped contract of qlinear_s8_grouped_stream (C-ABI pq_qlinear_w4_grouped_stream)
+def _grouped_call(what: str, xq, w4, gs, offsets, row_index):
+    """the checks of the grouped W4 entries: (xq, w4 as the kernel walks it, E, N, Kp, M_total, the C-ABI's operand arguments up to gs_expert_stride)"""
+    _on_gpu(what, xq=xq, w4=w4, gs=gs)
+    dev = xq.device
+    _check_operand(w4, "w4", dev, torch.uint8); _check_operand(gs, "gs", dev, torch.uint8)
+    if w4.dim() != 3 or w4.shape[0] == 0 or w4.shape[2] == 0 or w4.shape[2] % (GROUP // 2):
+        raise ValueError(f"{what}: w4 must be uint8 [E, N, Kp / 2] with Kp a positive multiple of {GROUP}, got shape {tuple(w4.shape)}")
+    E, N, G = w4.shape[0], w4.shape[1], w4.shape[2] // (GROUP // 2)
+    quads = (N + 3) // 4
+    if tuple(gs.shape) != (E, quads, G, 4) or not gs.is_contiguous():
+        raise ValueError(f"{what}: gs must be a contiguous uint8 [{E}, {quads}, {G}, 4] tensor, got shape {tuple(gs.shape)} stride {gs.stride()}")
+    if w4.stride(2) != 1 or w4.data_ptr() % 16 or (N > 1 and w4.stride(1) % 16) or (E > 1 and w4.stride(0) % 16):
+        w4 = w4.contiguous()
+    xq = _codes(what, xq, G * GROUP)
+    _check_operand(offsets, "offsets", dev, torch.int32, E + 1)
+    M = xq.shape[0]
+    if row_index is not None:
+        if row_index.dim() != 1:
+            raise ValueError(f"row_index must be a vector, got shape {tuple(row_index.shape)}")
+        _check_operand(row_index, "row_index", dev, torch.int32, row_index.numel())
+        M = row_index.numel()
+    ldw4 = w4.stride(1) if N > 1 else G * (GROUP // 2)
+    args = (xq.data_ptr(), L.ld(xq), _ptr(row_index), xq.shape[0]), (w4.data_ptr(), ldw4, w4.stride(0) if E > 1 else max(N, 1) * ldw4, gs.data_ptr(), quads * G * 4)
+    return xq, w4, E, N, G * GROUP, M, args
+
+
+def int_mm_w4_grouped(xq: torch.Tensor, w4: torch.Tensor, gs: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None) -> torch.Tensor:
+    """acc[r] = xq[src(r)] . W8[e(r)]^T, exact int32, by the grouped weight-streaming int4 kernel (C-ABI pq_gemm_s8w4s32_grouped_stream; at most 64 grouped rows) —
+    int_mm_grouped_stream on the stacked w4_expand outputs.  Rows >= offsets[E] are left as allocated."""
+    what = "int_mm_w4_grouped"
+    xq, w4, E, N, kp, M, (x_args, w_args) = _grouped_call(what, xq, w4, gs, offsets, row_index)
+    if M > STREAM_ROWS_MAX:
+        raise ValueError(f"{what}: at most {STREAM_ROWS_MAX} grouped rows, got {M} (int_mm_grouped on the expanded weights takes any number)")
+    acc = torch.empty((M, N), dtype=torch.int32, device=xq.device)
+    if M and N:
+        _launch(what, xq.device, L.lib().pq_gemm_s8w4s32_grouped_stream, *x_args, *w_args, offsets.data_ptr(), E, M, N, kp, acc.data_ptr(), N, L.stream_ptr(xq))
+    return acc
+
+
+def qlinear_w4_grouped(xq: torch.Tensor, xs: torch.Tensor, w4: torch.Tensor, gs: torch.Tensor, ws: torch.Tensor, bias, offsets: torch.Tensor, out_dtype,
+                       row_index: torch.Tensor | None = None, out: torch.Tensor | None = None, stream_rows: int = STREAM_ROWS_MAX) -> torch.Tensor:
+    """qlinear_s8_grouped(xq, xs, W8, ws, bias, offsets, out_dtype, row_index) bit for bit, W8[e] = w4_expand(w4[e], gs[e]): the operands and the contract of
+    qlinear_s8_grouped (rows sorted by expert, offsets int32 [E + 1] and row_index on the device and never read on the host, xs [M_total] in grouped order, rows >=
+    offsets[E] untouched) with the experts' weights stacked in the W4 format: w4 u8 [E, N, Kp / 2], gs u8 [E, ceil(N / 4), Kp / 128, 4], ws [E, N], bias [E, N] or None.
+    Up to `stream_rows` grouped rows (at most 64; 0: never) ONE launch of the grouped weight-streaming int4 kernel reads the live experts' packed weights (C-ABI
+    pq_qlinear_w4_grouped_stream).  More rows: ALL E experts are expanded into the cached workspace (qlinear._workspace) — E * N * Kp bytes, the size of the int8
+    weight the module does not keep: 0.94 GB for eight 28672 x 4096 experts; the price of having no second prefill kernel family, as in the dense path — in one launch
+    of pq_w4_expand where N % 4 == 0 (the stacked rows then share one quad layout), expert by expert otherwise, and qlinear_s8_grouped's tiles run on that.
+    xq: int8 [R, Kp] — codes with a zeroed tail where K < Kp."""
+    what = "qlinear_w4_grouped"
+    xq, w4, E, N, kp, M, (x_args, w_args) = _grouped_call(what, xq, w4, gs, offsets, row_index)
+    dev = xq.device
+    code = L.dtype_code(out_dtype)
+    _check_operand(xs, "xs", dev, torch.float32, M)
+    _check_operand(ws, "ws", dev, torch.float32)
+    if bias is not None:
+        if bias.dtype != out_dtype:
+            bias = bias.to(out_dtype)
+        _check_operand(bias, "bias", dev, out_dtype)
+    for t, name in ((ws, "ws"), (bias, "bias")):
+        if t is not None and (tuple(t.shape) != (E, N) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous [{E}, {N}] tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+    if out is not None:
+        _check_operand(out, "out", dev, out_dtype)
+        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
+    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M > min(stream_rows, STREAM_ROWS_MAX) and N:
+        w8 = _workspace(dev, E * N * kp)[:E * N * kp].view(torch.int8).view(E, N, kp)
+        if N % 4 == 0 and (E == 1 or w4.stride(0) == N * w4.stride(1)):
+            _expand_into(what, w4.as_strided((E * N, kp // 2), (w4.stride(1), 1)), gs, E * N, kp, w8)
+        else:
+            for e in range(E):
+                _expand_into(what, w4[e], gs[e], N, kp, w8[e])
+        return qlinear_s8_grouped(xq, xs, w8, ws, bias, offsets, out_dtype, row_index=row_index, out=y)
+    if M and N:
+        _launch(what, dev, L.lib().pq_qlinear_w4_grouped_stream, *x_args[:4], xs.data_ptr(), *w_args, ws.data_ptr(), _ptr(bias), offsets.data_ptr(), E, M, N, kp,
+                y.data_ptr(), L.ld(y), code, L.stream_ptr(xq))
+    return y
+
+
+class GroupedQLinearW4(nn.Module):
+    """A GroupedQLinear whose E experts' weights are kept in the W4 format: buffers `w4` [E, N, Kp / 2], `gs` [E, ceil(N / 4), Kp / 128, 4], `ws` [E, N], `bias` [E, N]
+    or None (no `wq`) — half the expert memory, and at decode about 0.51 of the weight bytes a step streams.  forward has GroupedQLinear.forward's signature and checks;
+    y has the bits of a GroupedQLinear that holds the expanded weights.  stream_rows (settable per instance): up to that many grouped rows take the streaming int4
+    kernel, more (or stream_rows = 0: all) expand into the workspace and run the int8 tiles (qlinear_w4_grouped).  state_dict round-trips through the buffers."""
+
+    stream_rows = STREAM_ROWS_MAX
+
+    def __init__(self, num_experts: int, in_features: int, out_features: int, bias: bool = False, device=None, dtype=None):
+        super().__init__()
+        self.num_experts, self.in_features, self.out_features = num_experts, in_features, out_features
+        kp = _round_k(in_features)
+        self.register_buffer("w4", torch.zeros((num_experts, out_features, kp // 2), dtype=torch.uint8, device=device))
+        self.register_buffer("gs", torch.ones((num_experts, (out_features + 3) // 4, kp // GROUP, 4), dtype=torch.uint8, device=device))
+        self.register_buffer("ws", torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
+        if bias:
+            self.register_buffer("bias", torch.zeros((num_experts, out_features), dtype=dtype or torch.bfloat16, device=device))
+        else:
+            self.bias = None
+
+    @classmethod
+    def from_grouped(cls, m: GroupedQLinear) -> "GroupedQLinearW4":
+        """the level-2 codes of m's [E, N, K] int8 weight: ONE w4_pack over its E * N rows, the multipliers re-laid from the quads of the stacked rows into each expert's
+        own ceil(N / 4) quads (rows past N hold 1) — per expert exactly w4_pack(m.wq[e]); ws and bias are m's own tensors"""
+        if not isinstance(m, GroupedQLinear):
+            raise TypeError(f"GroupedQLinearW4.from_grouped: expected a GroupedQLinear, got {type(m).__name__}")
+        E, N, K = m.num_experts, m.out_features, m.in_features
+        r = cls.__new__(cls)
+        nn.Module.__init__(r)
+        r.num_experts, r.in_features, r.out_features = E, K, N
+        w4, gs = w4_pack(m.wq.reshape(E * N, K))
+        G, quads = gs.shape[1], (N + 3) // 4
+        g = gs.permute(0, 2, 1).reshape(-1, G)[:E * N].reshape(E, N, G)          # g[e, n, j]
+        g = torch.cat([g, g.new_ones((E, quads * 4 - N, G))], dim=1)
+        r.register_buffer("w4", w4.view(E, N, -1))
+        r.register_buffer("gs", g.view(E, quads, 4, G).permute(0, 1, 3, 2).contiguous())
+        r.register_buffer("ws", m.ws)
+        if m.bias is not None:
+            r.register_buffer("bias", m.bias)
+        else:
+            r.bias = None
+        return r
+
+    @classmethod
+    def from_weight(cls, weight: torch.Tensor, bias=None) -> "GroupedQLinearW4":
+        """exactly the level-1 codes GroupedQLinear.from_weight makes, then packed"""
+        return cls.from_grouped(GroupedQLinear.from_weight(weight, bias))
+
+    @classmethod
+    def from_linears(cls, linears) -> "GroupedQLinearW4":
+        return cls.from_grouped(GroupedQLinear.from_linears(linears))
+
+    codes_for_gemm = GroupedQLinear.codes_for_gemm          # (zero-tailed codes where in_features is not a multiple of 128: the packed tail holds zeros)
+
+    def forward(self, xq: QTensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, xs: torch.Tensor | None = None) -> torch.Tensor:
+        if not isinstance(xq, QTensor) or xq.axis != 1 or xq.shape[-1] != self.in_features:
+            raise ValueError("GroupedQLinearW4: input must be a per-token QTensor [R, in_features]")
+        codes = self.codes_for_gemm(xq.int_data.reshape(-1, self.in_features))
+        if xs is None:
+            xs = xq.scale if row_index is None else xq.scale.index_select(0, row_index)
+        return qlinear_w4_grouped(codes, xs, self.w4, self.gs, self.ws, self.bias, offsets, xq.orig_dtype, row_index=row_index, stream_rows=self.stream_rows)
+
+    def extra_repr(self):
+        return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, w4, "
+                f"stream_rows={self.stream_rows}")
+
+
+def swap_moe_experts_w4(model: nn.Module, predicate=None) -> int:
+    """Replace, in place, the two GroupedQLinear members (gate_up, down) of every MoEGatedMLP of `model` for which predicate(name, module) is true (None: all) by
+    GroupedQLinearW4.from_grouped; returns the number of MoEGatedMLP modules converted (a second call: 0).  `name` is the module's name in its parent, as in
+    swap_linears_w4.  Opt-in; call it AFTER swap_moe_experts (which makes the MoEGatedMLP modules).  Gate kinds, the router, fuse_moe_routers and torch_plumbing are
+    untouched: MoEGatedMLP reads only num_experts / in_features / out_features of its members and calls them."""
+    n = 0
+    for name, child in list(model.named_children()):
+        if isinstance(child, MoEGatedMLP):
+            if isinstance(child.gate_up, GroupedQLinear) and isinstance(child.down, GroupedQLinear) and (predicate is None or predicate(name, child)):
+                child.gate_up, child.down = GroupedQLinearW4.from_grouped(child.gate_up), GroupedQLinearW4.from_grouped(child.down)
+                n += 1
+        else:
+            n += swap_moe_experts_w4(child, predicate)
     return n
