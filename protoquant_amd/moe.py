@@ -28,7 +28,8 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .qlinear import FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8_grouped, qlinear_s8_grouped_stream
+from .qlinear import (FusedQLinear, GatedMLP, _check_operand, _is_silu, _KPadded, _module_of, _round_k, _set_buffers, _workspace, _zero_tailed, is_plain_linear, qlinear,
+                      qlinear_s8_grouped, qlinear_s8_grouped_stream)
 from .qtensor import QTensor, glu_params, glu_quantize, quantize, silu_mul_quantize
 
 
@@ -49,25 +50,14 @@ class GroupedQLinear(_KPadded, nn.Module):
     def __init__(self, num_experts: int, in_features: int, out_features: int, bias: bool = False, device=None, dtype=None):
         super().__init__()
         self.num_experts, self.in_features, self.out_features = num_experts, in_features, out_features
-        dtype = dtype or torch.bfloat16
-        self.register_buffer("wq", torch.zeros((num_experts, out_features, in_features), dtype=torch.int8, device=device))
-        self.register_buffer("ws", torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
-        if bias:
-            self.register_buffer("bias", torch.zeros((num_experts, out_features), dtype=dtype, device=device))
-        else:
-            self.bias = None
+        _set_buffers(self, torch.zeros((num_experts, out_features), dtype=dtype or torch.bfloat16, device=device) if bias else None,
+                     wq=torch.zeros((num_experts, out_features, in_features), dtype=torch.int8, device=device),
+                     ws=torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
 
     @classmethod
     def _from_parts(cls, wq: torch.Tensor, ws: torch.Tensor, bias) -> "GroupedQLinear":
-        m = cls.__new__(cls)
-        nn.Module.__init__(m)
+        m = _module_of(cls, bias.contiguous() if bias is not None else None, wq=wq.contiguous(), ws=ws.contiguous())
         m.num_experts, m.out_features, m.in_features = wq.shape
-        m.register_buffer("wq", wq.contiguous())
-        m.register_buffer("ws", ws.contiguous())
-        if bias is not None:
-            m.register_buffer("bias", bias.contiguous())
-        else:
-            m.bias = None
         return m
 
     @classmethod
@@ -96,13 +86,7 @@ class GroupedQLinear(_KPadded, nn.Module):
 
     def codes_for_gemm(self, codes: torch.Tensor) -> torch.Tensor:
         """int8 [R, in_features] -> the operand the grouped GEMM reads: itself, or a zero-tailed copy of the next multiple of 128 columns"""
-        K, kp = self.in_features, _round_k(self.in_features)
-        if kp == K:
-            return codes
-        buf = torch.empty((codes.shape[0], kp), dtype=torch.int8, device=codes.device)
-        buf[:, :K].copy_(codes)
-        buf[:, K:].zero_()
-        return buf
+        return codes if self.in_features % 128 == 0 else _zero_tailed(codes, _round_k(self.in_features))
 
     def forward(self, xq: QTensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None, xs: torch.Tensor | None = None) -> torch.Tensor:
         """xq: per-token QTensor [R, in_features].  Without row_index its rows are the grouped rows themselves; with it grouped row r reads row row_index[r] of xq and xs

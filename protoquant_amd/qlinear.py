@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .qtensor import QTensor, gelu_mul_quantize, quantize, silu_mul_quantize
+from .qtensor import QTensor, _launch, _ptr, gelu_mul_quantize, quantize, silu_mul_quantize
 
 
 def int_mm(xq: torch.Tensor, wq: torch.Tensor) -> torch.Tensor:
@@ -23,11 +23,9 @@ def int_mm(xq: torch.Tensor, wq: torch.Tensor) -> torch.Tensor:
         raise ValueError("int_mm expects int8 [M,K] and int8 [N,K]")
     if _pad_pays(M, N, K):
         K = _round_k(K)
-        xq, wq = _pad_k(xq, K), _pad_k(wq, K)
+        xq, wq = _zero_tailed(xq, K), _zero_tailed(wq, K)
     acc = torch.empty((M, N), dtype=torch.int32, device=xq.device)
-    with torch.cuda.device(xq.device):
-        L.check(L.lib().pq_gemm_s8s8s32(xq.data_ptr(), L.ld(xq), wq.data_ptr(), L.ld(wq), acc.data_ptr(), max(N, 1),
-                                        M, N, K, L.stream_ptr(xq)), "int_mm")
+    _launch("int_mm", xq.device, L.lib().pq_gemm_s8s8s32, xq.data_ptr(), L.ld(xq), wq.data_ptr(), L.ld(wq), acc.data_ptr(), max(N, 1), M, N, K, L.stream_ptr(xq))
     return acc
 
 
@@ -76,13 +74,31 @@ def _round_k(K: int) -> int:
     return -(-K // 128) * 128
 
 
-def _pad_k(t: torch.Tensor, kp: int) -> torch.Tensor:
-    """[rows, K] int8 -> a fresh [rows, kp] copy with a zeroed tail."""
-    K = t.shape[1]
-    buf = torch.empty((t.shape[0], kp), dtype=torch.int8, device=t.device)
-    buf[:, :K].copy_(t)
+def _zero_tailed(codes: torch.Tensor, kp: int) -> torch.Tensor:
+    """int8 codes [M, K] -> the operand a GEMM over kp >= K columns reads: the codes themselves when kp == K, else a fresh [M, kp] buffer with a zeroed tail (zeros add
+    nothing to an integer sum)"""
+    K = codes.shape[1]
+    if kp == K:
+        return codes
+    buf = torch.empty((codes.shape[0], kp), dtype=torch.int8, device=codes.device)
+    buf[:, :K].copy_(codes)
     buf[:, K:].zero_()
     return buf
+
+
+def _quantize_zero_tailed(x: torch.Tensor, kp: int, where: str):
+    """float rows x[..., K] -> (codes int8 [M, kp], xs f32 [M]): kernel K1 quantises per token straight into a buffer of kp >= K columns whose tail is zeroed"""
+    L.require_gpu(x, where)
+    code = L.dtype_code(x.dtype)
+    K = x.shape[-1]
+    x2 = L.row_major_2d(x.reshape(-1, K))
+    M = x2.shape[0]
+    buf = torch.empty((M, kp), dtype=torch.int8, device=x.device)
+    if kp != K:
+        buf[:, K:].zero_()
+    xs = torch.empty((M,), dtype=torch.float32, device=x.device)
+    _launch("quantize", x.device, L.lib().pq_quant_rowwise, x2.data_ptr(), code, M, K, L.ld(x2), buf.data_ptr(), kp, xs.data_ptr(), L.stream_ptr(x))
+    return buf, xs
 
 
 def _pad_pays(M: int, N: int, K: int) -> bool:
@@ -93,72 +109,95 @@ def _pad_pays(M: int, N: int, K: int) -> bool:
     return K % 128 != 0 and K > 0 and M * N * K >= (1 << 31)
 
 
-def qlinear_s8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, out_dtype,
-               out: torch.Tensor | None = None) -> torch.Tensor:
-    """Fused int8 GEMM + dequant epilogue on pre-quantised operands (C-ABI pq_qlinear_s8)."""
-    L.require_gpu(xq, "qlinear_s8(xq)")
+# The entries below are the host side of a launch-bound decode step: a helper is called where it stands for several checks, L.require_gpu and the dtype checks of the codes
+# only once a cheap test says they will refuse, and a fresh output is allocated in place.
+def _out(out: torch.Tensor, rows: int, cols: int, dev, dtype, terse: bool = False) -> torch.Tensor:
+    """A caller's `out`, refused unless it is a row-major [rows, cols] tensor of `dtype` on `dev`.  terse: qlinear_s8_t's and qlinear_s8_kslabs' one refusal"""
+    if terse:
+        if out.device != dev or out.dtype != dtype or out.shape != (rows, cols) or (cols > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a row-major [{rows}, {cols}] {dtype} tensor on {dev}")
+        return out
+    _check_operand(out, "out", dev, dtype)
+    if out.dim() != 2 or out.shape != (rows, cols) or (cols > 1 and out.stride(1) != 1):
+        raise ValueError(f"out must be a row-major [{rows}, {cols}] tensor, got {tuple(out.shape)} stride {out.stride()}")
+    return out
+
+
+def _epilogue_operands(dev, out_dtype, xs, M: int, ws, bias, per):
+    """What every fused entry checks about its epilogue, in this order: the bias cast to out_dtype; xs f32 [M] (None: the entry makes its own); ws f32 and bias — vectors
+    of `per` elements, or contiguous [E, N] tensors where `per` is that shape (the grouped entries).  Returns the bias the library reads."""
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    if xs is not None:
+        _check_operand(xs, "xs", dev, torch.float32, M)
+    if type(per) is int:
+        _check_operand(ws, "ws", dev, torch.float32, per)
+        if bias is not None:
+            _check_operand(bias, "bias", dev, out_dtype, per)
+        return bias
+    _check_operand(ws, "ws", dev, torch.float32)
+    if bias is not None:
+        _check_operand(bias, "bias", dev, out_dtype)
+    ws_fits = tuple(ws.shape) == per and ws.is_contiguous()
+    if not ws_fits or (bias is not None and (tuple(bias.shape) != per or not bias.is_contiguous())):
+        name, t = ("bias", bias) if ws_fits else ("ws", ws)
+        raise ValueError(f"{name} must be a contiguous [{per[0]}, {per[1]}] tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+    return bias
+
+
+def _launch_with_workspace(what: str, on: torch.Tensor, entry, query, qargs, *args, at_least: int = 0):
+    """Query, workspace, launch: entry(*args, workspace | NULL, its bytes, stream) on the current stream of `on`'s device, with the bytes query(*qargs) asks for out of the
+    cached workspace.  Query and launch run under the tensor's device: the planner's thresholds follow the CURRENT device's CU count.  at_least: the entry always wants a
+    workspace, of that many bytes or more, and is told the size of the one it gets (pq_qlinear_dyn)."""
+    dev = on.device
+    with torch.cuda.device(dev):
+        wbytes = query(*qargs)          # > 0: split-K pays for this shape (or the entry keeps codes and scales there)
+        if at_least:
+            wsp = _workspace(dev, max(wbytes, at_least))
+            L.check(entry(*args, wsp.data_ptr(), wsp.numel(), L.stream_ptr(on)), what)
+        else:
+            L.check(entry(*args, _workspace(dev, wbytes).data_ptr() if wbytes else None, wbytes, L.stream_ptr(on)), what)
+
+
+def _qlinear_s8(what: str, transposed: bool, xq, xs, wq, ws, bias, out_dtype, out):
+    """qlinear_s8 / qlinear_s8_t: the output [M, N] or [N, M]"""
     xq, wq = L.row_major_2d(xq), L.row_major_2d(wq)
     M, K = xq.shape
     N = wq.shape[0]
     if wq.shape[1] != K:
         raise ValueError(f"shape mismatch: x has K={K}, weight has K={wq.shape[1]}")
     code = L.dtype_code(out_dtype)
-    if bias is not None and bias.dtype != out_dtype:
-        bias = bias.to(out_dtype)
     dev = xq.device
-    _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
-    _check_operand(xs, "xs", dev, torch.float32, M); _check_operand(ws, "ws", dev, torch.float32, N)
-    if _pad_pays(M, N, K):
+    if xq.dtype != torch.int8 or wq.dtype != torch.int8 or wq.device != dev:
+        _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
+    bias = _epilogue_operands(dev, out_dtype, xs, M, ws, bias, per=N)
+    rows, cols = (N, M) if transposed else (M, N)
+    y = torch.empty((rows, cols), dtype=out_dtype, device=dev) if out is None else _out(out, rows, cols, dev, out_dtype, terse=transposed)
+    if K % 128 and _pad_pays(M, N, K):
         K = _round_k(K)
-        xq, wq = _pad_k(xq, K), _pad_k(wq, K)
-    if bias is not None:
-        _check_operand(bias, "bias", dev, out_dtype, N)
-    if out is not None:
-        _check_operand(out, "out", dev, out_dtype)
-        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
-    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=xq.device)
-    with torch.cuda.device(xq.device):          # (the planner's thresholds follow the CURRENT device's CU count: query and launch under the tensor's device)
-        wbytes = L.lib().pq_qlinear_workspace_bytes(M, N, K)        # > 0: split-K pays for this shape
-        wsp = _workspace(xq.device, wbytes) if wbytes else None
-        L.check(L.lib().pq_qlinear_s8(xq.data_ptr(), L.ld(xq), xs.data_ptr(), wq.data_ptr(), L.ld(wq), ws.data_ptr(),
-                                      bias.data_ptr() if bias is not None else None, y.data_ptr(), L.ld(y), code,
-                                      M, N, K, wsp.data_ptr() if wsp is not None else None, wbytes,
-                                      L.stream_ptr(xq)), "qlinear_s8")
+        xq, wq = _zero_tailed(xq, K), _zero_tailed(wq, K)
+    lib = L.lib()
+    entry, query = (lib.pq_qlinear_s8_t, lib.pq_qlinear_t_workspace_bytes) if transposed else (lib.pq_qlinear_s8, lib.pq_qlinear_workspace_bytes)
+    _launch_with_workspace(what, xq, entry, query, (M, N, K), xq.data_ptr(), L.ld(xq), xs.data_ptr(), wq.data_ptr(), L.ld(wq), ws.data_ptr(),
+                           bias.data_ptr() if bias is not None else None, y.data_ptr(), L.ld(y), code, M, N, K)
     return y
+
+
+def qlinear_s8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, out_dtype,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Fused int8 GEMM + dequant epilogue on pre-quantised operands (C-ABI pq_qlinear_s8)."""
+    if not xq.is_cuda:
+        L.require_gpu(xq, "qlinear_s8(xq)")
+    return _qlinear_s8("qlinear_s8", False, xq, xs, wq, ws, bias, out_dtype, out)
 
 
 def qlinear_s8_t(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, out_dtype,
                  out: torch.Tensor | None = None) -> torch.Tensor:
     """The same fused GEMM + epilogue with the output TRANSPOSED: returns yt[N, M], yt[n][m] bit-identical to
     qlinear_s8(...)[m][n] (C-ABI pq_qlinear_s8_t).  The column-sharded configuration gathers these row blocks contiguously."""
-    L.require_gpu(xq, "qlinear_s8_t(xq)")
-    xq, wq = L.row_major_2d(xq), L.row_major_2d(wq)
-    M, K = xq.shape
-    N = wq.shape[0]
-    if wq.shape[1] != K:
-        raise ValueError(f"shape mismatch: x has K={K}, weight has K={wq.shape[1]}")
-    code = L.dtype_code(out_dtype)
-    if bias is not None and bias.dtype != out_dtype:
-        bias = bias.to(out_dtype)
-    dev = xq.device
-    _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
-    _check_operand(xs, "xs", dev, torch.float32, M); _check_operand(ws, "ws", dev, torch.float32, N)
-    if _pad_pays(M, N, K):
-        K = _round_k(K)
-        xq, wq = _pad_k(xq, K), _pad_k(wq, K)
-    if bias is not None:
-        _check_operand(bias, "bias", dev, out_dtype, N)
-    if out is not None and (out.device != dev or out.dtype != out_dtype or out.shape != (N, M) or (M > 1 and out.stride(1) != 1)):
-        raise ValueError(f"out must be a row-major [{N}, {M}] {out_dtype} tensor on {dev}")
-    yt = out if out is not None else torch.empty((N, M), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        wbytes = L.lib().pq_qlinear_t_workspace_bytes(M, N, K)
-        wsp = _workspace(dev, wbytes) if wbytes else None
-        L.check(L.lib().pq_qlinear_s8_t(xq.data_ptr(), L.ld(xq), xs.data_ptr(), wq.data_ptr(), L.ld(wq), ws.data_ptr(),
-                                        bias.data_ptr() if bias is not None else None, yt.data_ptr(), L.ld(yt), code,
-                                        M, N, K, wsp.data_ptr() if wsp is not None else None, wbytes, L.stream_ptr(xq)), "qlinear_s8_t")
-    return yt
+    if not xq.is_cuda:
+        L.require_gpu(xq, "qlinear_s8_t(xq)")
+    return _qlinear_s8("qlinear_s8_t", True, xq, xs, wq, ws, bias, out_dtype, out)
 
 
 def qlinear_s8_kslabs(xq_stacked: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias, out_dtype,
@@ -177,34 +216,44 @@ def qlinear_s8_kslabs(xq_stacked: torch.Tensor, xs: torch.Tensor, wq: torch.Tens
     if wq.shape[1] != K:
         raise ValueError(f"shape mismatch: stacked x has K={K}, weight has K={wq.shape[1]}")
     code = L.dtype_code(out_dtype)
-    if bias is not None and bias.dtype != out_dtype:
-        bias = bias.to(out_dtype)
     dev = xq_stacked.device
     _check_operand(xq_stacked, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
-    _check_operand(xs, "xs", dev, torch.float32, M); _check_operand(ws, "ws", dev, torch.float32, N)
-    if bias is not None:
-        _check_operand(bias, "bias", dev, out_dtype, N)
-    if out is not None and (out.device != dev or out.dtype != out_dtype or out.shape != (M, N) or (N > 1 and out.stride(1) != 1)):
-        raise ValueError(f"out must be a row-major [{M}, {N}] {out_dtype} tensor on {dev}")
-    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        # the exact query (it looks at the operands' alignment and strides): the fused split-K's hand-over slabs where the 256 x 256 tile walks the blocks in place,
-        # nothing where a ring tile does, the layout pass's M * K bytes otherwise
-        wbytes = L.lib().pq_qlinear_kslabs_workspace_bytes_for(xq_stacked.data_ptr(), kps, M * kps, kps, wq.data_ptr(), L.ld(wq), M, N, K)
-        wsp = _workspace(dev, wbytes) if wbytes else None
-        L.check(L.lib().pq_qlinear_s8_kslabs(xq_stacked.data_ptr(), kps, M * kps, kps, xs.data_ptr(), wq.data_ptr(), L.ld(wq), ws.data_ptr(),
-                                             bias.data_ptr() if bias is not None else None, y.data_ptr(), L.ld(y), code, M, N, K,
-                                             wsp.data_ptr() if wsp is not None else None, wbytes, L.stream_ptr(xq_stacked)), "qlinear_s8_kslabs")
+    bias = _epilogue_operands(dev, out_dtype, xs, M, ws, bias, per=N)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev) if out is None else _out(out, M, N, dev, out_dtype, terse=True)
+    slabs = (xq_stacked.data_ptr(), kps, M * kps, kps)
+    # the exact query (it looks at the operands' alignment and strides): the fused split-K's hand-over slabs where the 256 x 256 tile walks the blocks in place,
+    # nothing where a ring tile does, the layout pass's M * K bytes otherwise
+    _launch_with_workspace("qlinear_s8_kslabs", xq_stacked, L.lib().pq_qlinear_s8_kslabs, L.lib().pq_qlinear_kslabs_workspace_bytes_for,
+                           (*slabs, wq.data_ptr(), L.ld(wq), M, N, K), *slabs, xs.data_ptr(), wq.data_ptr(), L.ld(wq), ws.data_ptr(), _ptr(bias), y.data_ptr(), L.ld(y),
+                           code, M, N, K)
     return y
 
 
+def _grouped_rows(xq, w, width: int, offsets, row_index):
+    """What the grouped entries, int8 and int4, share once xq [R, K] and the stacked weight w [E, N, width] (int8 codes, or packed int4: K / 2 bytes a row) have passed
+    their own checks: offsets int32 [E + 1] and row_index int32 [M_total] are contiguous device vectors.  Returns the C-ABI's x-side arguments and its weight-side ones
+    (pointer, row pitch, expert stride)."""
+    dev = xq.device
+    E, N = w.shape[0], w.shape[1]
+    _check_operand(offsets, "offsets", dev, torch.int32, E + 1)
+    if row_index is not None:
+        if row_index.dim() != 1:
+            raise ValueError(f"row_index must be a vector, got shape {tuple(row_index.shape)}")
+        _check_operand(row_index, "row_index", dev, torch.int32, row_index.numel())
+    ldw = w.stride(1) if N > 1 else width
+    return ((xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0]),
+            (w.data_ptr(), ldw, w.stride(0) if E > 1 else N * ldw))
+
+
 def _grouped_operands(what: str, xq, wq, offsets, row_index):
-    """Shared checks of the grouped entry points: xq int8 [R, K] row-major, wq int8 [E, N, K] (K contiguous, one stride between experts), offsets int32 [E + 1] and
-    row_index int32 [M_total] contiguous device vectors.  Returns (xq, wq, E, N, K, M_total)."""
-    L.require_gpu(xq, f"{what}(xq)")
+    """Shared checks of the grouped int8 entry points: xq int8 [R, K] row-major, wq int8 [E, N, K] (K contiguous, one stride between experts).  Returns (xq, wq as the
+    kernels walk them — the caller keeps both alive over the launch —, E, N, K, M_total); offsets and row_index are _grouped_rows' to check."""
+    if not xq.is_cuda:
+        L.require_gpu(xq, f"{what}(xq)")
     xq = L.row_major_2d(xq)
     dev = xq.device
-    _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
+    if xq.dtype != torch.int8 or wq.dtype != torch.int8 or wq.device != dev:
+        _check_operand(xq, "xq", dev, torch.int8); _check_operand(wq, "wq", dev, torch.int8)
     if wq.dim() != 3:
         raise ValueError(f"{what}: wq must be int8 [E, N, K], got shape {tuple(wq.shape)}")
     E, N, K = wq.shape
@@ -214,15 +263,7 @@ def _grouped_operands(what: str, xq, wq, offsets, row_index):
         raise ValueError(f"{what}: K = {K} must be a positive multiple of 128 (GroupedQLinear pads its weights; pad the codes with zeros)")
     if (K > 1 and wq.stride(2) != 1) or (N > 1 and wq.stride(1) < K) or (E > 1 and wq.stride(0) < N * wq.stride(1)):
         wq = wq.contiguous()
-    _check_operand(offsets, "offsets", dev, torch.int32, E + 1)
-    if row_index is not None:
-        if row_index.dim() != 1:
-            raise ValueError(f"row_index must be a vector, got shape {tuple(row_index.shape)}")
-        _check_operand(row_index, "row_index", dev, torch.int32, row_index.numel())
-        M_total = row_index.numel()
-    else:
-        M_total = xq.shape[0]
-    return xq, wq, E, N, K, M_total
+    return xq, wq, E, N, K, (xq.shape[0] if row_index is None else row_index.numel())
 
 
 def _qlinear_s8_grouped(what: str, max_rows, xq, xs, wq, ws, bias, offsets, out_dtype, row_index, out):
@@ -230,28 +271,14 @@ def _qlinear_s8_grouped(what: str, max_rows, xq, xs, wq, ws, bias, offsets, out_
     xq, wq, E, N, K, M = _grouped_operands(what, xq, wq, offsets, row_index)
     if max_rows is not None and M > max_rows:
         raise ValueError(f"{what}: at most {max_rows} grouped rows, got {M} (qlinear_s8_grouped takes any number)")
+    x_args, w_args = _grouped_rows(xq, wq, K, offsets, row_index)
     dev = xq.device
     code = L.dtype_code(out_dtype)
-    _check_operand(xs, "xs", dev, torch.float32, M)
-    _check_operand(ws, "ws", dev, torch.float32)
-    if tuple(ws.shape) != (E, N) or not ws.is_contiguous():
-        raise ValueError(f"ws must be a contiguous [{E}, {N}] tensor, got shape {tuple(ws.shape)} stride {ws.stride()}")
-    if bias is not None:
-        if bias.dtype != out_dtype:
-            bias = bias.to(out_dtype)
-        _check_operand(bias, "bias", dev, out_dtype)
-        if tuple(bias.shape) != (E, N) or not bias.is_contiguous():
-            raise ValueError(f"bias must be a contiguous [{E}, {N}] tensor, got shape {tuple(bias.shape)} stride {bias.stride()}")
-    if out is not None:
-        _check_operand(out, "out", dev, out_dtype)
-        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
-    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
+    bias = _epilogue_operands(dev, out_dtype, xs, M, ws, bias, per=(E, N))
+    y = torch.empty((M, N), dtype=out_dtype, device=dev) if out is None else _out(out, M, N, dev, out_dtype)
     with torch.cuda.device(dev):
-        L.check(getattr(L.lib(), "pq_" + what)(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0], xs.data_ptr(),
-                                               wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K), ws.data_ptr(),
-                                               bias.data_ptr() if bias is not None else None, offsets.data_ptr(), E, M, N, K, y.data_ptr(), L.ld(y), code,
-                                               L.stream_ptr(xq)), what)
+        L.check(getattr(L.lib(), "pq_" + what)(*x_args, xs.data_ptr(), *w_args, ws.data_ptr(), bias.data_ptr() if bias is not None else None, offsets.data_ptr(),
+                                               E, M, N, K, y.data_ptr(), L.ld(y), code, L.stream_ptr(xq)), what)
     return y
 
 
@@ -259,16 +286,9 @@ def _int_mm_grouped(what: str, entry: str, max_rows, xq, wq, offsets, row_index,
     xq, wq, E, N, K, M = _grouped_operands(what, xq, wq, offsets, row_index)
     if max_rows is not None and M > max_rows:
         raise ValueError(f"{what}: at most {max_rows} grouped rows, got {M} (int_mm_grouped takes any number)")
-    dev = xq.device
-    if out is not None:
-        _check_operand(out, "out", dev, torch.int32)
-        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
-    acc = out if out is not None else torch.empty((M, N), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(getattr(L.lib(), entry)(xq.data_ptr(), L.ld(xq), row_index.data_ptr() if row_index is not None else None, xq.shape[0],
-                                        wq.data_ptr(), wq.stride(1) if N > 1 else K, wq.stride(0) if E > 1 else N * (wq.stride(1) if N > 1 else K),
-                                        offsets.data_ptr(), E, M, N, K, acc.data_ptr(), L.ld(acc), L.stream_ptr(xq)), what)
+    x_args, w_args = _grouped_rows(xq, wq, K, offsets, row_index)
+    acc = torch.empty((M, N), dtype=torch.int32, device=xq.device) if out is None else _out(out, M, N, xq.device, torch.int32)
+    _launch(what, xq.device, getattr(L.lib(), entry), *x_args, *w_args, offsets.data_ptr(), E, M, N, K, acc.data_ptr(), L.ld(acc), L.stream_ptr(xq))
     return acc
 
 
@@ -317,21 +337,15 @@ def qlinear_dyn(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias=None) 
     N = wq.shape[0]
     if wq.shape[1] != K:
         raise ValueError(f"shape mismatch: x has K={K}, weight has K={wq.shape[1]}")
-    if bias is not None and bias.dtype != x.dtype:
-        bias = bias.to(x.dtype)
-    _check_operand(wq, "wq", x.device, torch.int8); _check_operand(ws, "ws", x.device, torch.float32, N)
-    if bias is not None:
-        _check_operand(bias, "bias", x.device, x.dtype, N)
-    if _pad_pays(lead, N, K):
+    _check_operand(wq, "wq", x.device, torch.int8)
+    bias = _epilogue_operands(x.device, x.dtype, None, lead, ws, bias, per=N)
+    if K % 128 and _pad_pays(lead, N, K):
         xq = quantize(x2, axis=-1)
         return qlinear_s8(xq.int_data, xq.scale, wq, ws, bias, x.dtype).reshape(*x.shape[:-1], N)
     y = torch.empty((lead, N), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        wbytes = L.lib().pq_qlinear_dyn_workspace_bytes(lead, N, K)
-        wsp = _workspace(x.device, max(wbytes, 256))
-        L.check(L.lib().pq_qlinear_dyn(x2.data_ptr(), code, L.ld(x2), wq.data_ptr(), L.ld(wq), ws.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None, y.data_ptr(), max(N, 1),
-                                       lead, N, K, wsp.data_ptr(), wsp.numel(), L.stream_ptr(x)), "qlinear_dyn")
+    lib = L.lib()
+    _launch_with_workspace("qlinear_dyn", x, lib.pq_qlinear_dyn, lib.pq_qlinear_dyn_workspace_bytes, (lead, N, K), x2.data_ptr(), code, L.ld(x2),
+                           wq.data_ptr(), L.ld(wq), ws.data_ptr(), _ptr(bias), y.data_ptr(), max(N, 1), lead, N, K, at_least=256)
     return y.reshape(*x.shape[:-1], N)
 
 
@@ -372,43 +386,39 @@ class _KPadded:
 
     def _padded_forward(self, x, wq_pad, kp):
         """x: float [..., K] or a per-token QTensor; the GEMM runs over kp = round_up(K, 128) with zero tails on both operands."""
-        K, N = self.in_features, self.out_features
         if isinstance(x, QTensor):
-            src = L.row_major_2d(x.int_data.reshape(-1, K))
-            M = src.shape[0]
-            buf = torch.empty((M, kp), dtype=torch.int8, device=src.device)
-            buf[:, :K].copy_(src)
-            buf[:, K:].zero_()
-            xs, out_dtype = x.scale, x.orig_dtype
+            buf, xs, out_dtype = _zero_tailed(x.int_data.reshape(-1, self.in_features), kp), x.scale, x.orig_dtype
         else:
-            L.require_gpu(x, "qlinear(x)")
-            code = L.dtype_code(x.dtype)
-            lead = 1
-            for d in x.shape[:-1]:
-                lead *= d
-            x2 = L.row_major_2d(x.reshape(lead, K))
-            M = lead
-            buf = torch.empty((M, kp), dtype=torch.int8, device=x.device)
-            buf[:, K:].zero_()
-            xs = torch.empty((M,), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                L.check(L.lib().pq_quant_rowwise(x2.data_ptr(), code, M, K, L.ld(x2), buf.data_ptr(), kp, xs.data_ptr(), L.stream_ptr(x)), "quantize")
-            out_dtype = x.dtype
+            (buf, xs), out_dtype = _quantize_zero_tailed(x, kp, "qlinear(x)"), x.dtype
         y = qlinear_s8(buf, xs, wq_pad, self.ws, self.bias, out_dtype)
-        return y.reshape(*x.shape[:-1], N)
+        return y.reshape(*x.shape[:-1], self.out_features)
 
 
 def gemm_operands(local: "_KPadded", codes: torch.Tensor):
     """(codes, wq) for one GEMM of a module that owns `wq`: as they are when in_features is a multiple of 128, else both zero-padded to the next one (_KPadded).
     codes: int8 [M, in_features]."""
-    K = local.in_features
-    if K % 128 == 0 or not codes.is_cuda:      # (CPU stand-ins of the gloo host-logic tests pass through)
+    if local.in_features % 128 == 0 or not codes.is_cuda:      # (CPU stand-ins of the gloo host-logic tests pass through)
         return codes, local.wq
     wq, kp = local._wq_for_gemm()
-    buf = torch.empty((codes.shape[0], kp), dtype=torch.int8, device=codes.device)
-    buf[:, :K].copy_(codes)
-    buf[:, K:].zero_()
-    return buf, wq
+    return _zero_tailed(codes, kp), wq
+
+
+def _set_buffers(m: nn.Module, bias, **weights) -> nn.Module:
+    """the buffers of a quantised linear module, in state_dict order: the weight's tensors (wq | w4, gs; ws), then `bias` — a buffer, or the attribute None"""
+    for name, t in weights.items():
+        m.register_buffer(name, t)
+    if bias is not None:
+        m.register_buffer("bias", bias)
+    else:
+        m.bias = None
+    return m
+
+
+def _module_of(cls, bias, **weights) -> nn.Module:
+    """a `cls` made of existing tensors, past its __init__ (which would allocate them)"""
+    m = cls.__new__(cls)
+    nn.Module.__init__(m)
+    return _set_buffers(m, bias, **weights)
 
 
 class qlinear(_KPadded, nn.Module):
@@ -417,30 +427,15 @@ class qlinear(_KPadded, nn.Module):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
-        dtype = dtype or torch.bfloat16
-        self.register_buffer("wq", torch.zeros((out_features, in_features), dtype=torch.int8, device=device))
-        self.register_buffer("ws", torch.ones((out_features,), dtype=torch.float32, device=device))
-        if bias:
-            self.register_buffer("bias", torch.zeros((out_features,), dtype=dtype, device=device))
-        else:
-            self.bias = None
+        _set_buffers(self, torch.zeros((out_features,), dtype=dtype or torch.bfloat16, device=device) if bias else None,
+                     wq=torch.zeros((out_features, in_features), dtype=torch.int8, device=device), ws=torch.ones((out_features,), dtype=torch.float32, device=device))
 
     @classmethod
     def from_linear(cls, lin: nn.Linear) -> "qlinear":
         """Quantise lin.weight [N,K] per output channel on the GPU (kernel K1 over W's rows)."""
         w = lin.weight.detach()
         L.require_gpu(w, "qlinear.from_linear(weight)")
-        m = cls.__new__(cls)
-        nn.Module.__init__(m)
-        m.in_features, m.out_features = lin.in_features, lin.out_features
-        qw = quantize(w, axis=-1)
-        m.register_buffer("wq", qw.int_data)
-        m.register_buffer("ws", qw.scale)
-        if lin.bias is not None:
-            m.register_buffer("bias", lin.bias.detach().clone())
-        else:
-            m.bias = None
-        return m
+        return cls.from_qtensor(quantize(w, axis=-1), lin.bias.detach().clone() if lin.bias is not None else None)
 
     @classmethod
     def from_kn_weight(cls, weight_kn: torch.Tensor, bias=None) -> "qlinear":
@@ -460,15 +455,8 @@ class qlinear(_KPadded, nn.Module):
     def from_qtensor(cls, qw: QTensor, bias=None) -> "qlinear":
         if qw.axis != 1 or qw.int_data.dim() != 2:
             raise ValueError("weight QTensor must be [N,K] quantised per output channel (axis=-1)")
-        m = cls.__new__(cls)
-        nn.Module.__init__(m)
+        m = _module_of(cls, bias, wq=qw.int_data, ws=qw.scale)
         m.out_features, m.in_features = qw.int_data.shape
-        m.register_buffer("wq", qw.int_data)
-        m.register_buffer("ws", qw.scale)
-        if bias is not None:
-            m.register_buffer("bias", bias)
-        else:
-            m.bias = None
         return m
 
     def forward(self, x) -> torch.Tensor:
@@ -513,12 +501,8 @@ class FusedQLinear(_KPadded, nn.Module):
         self.in_features = parts[0].in_features
         self.splits = [p.out_features for p in parts]
         self.out_features = sum(self.splits)
-        self.register_buffer("wq", torch.cat([p.wq for p in parts], dim=0).contiguous())
-        self.register_buffer("ws", torch.cat([p.ws for p in parts], dim=0).contiguous())
-        if parts[0].bias is not None:
-            self.register_buffer("bias", torch.cat([p.bias for p in parts], dim=0).contiguous())
-        else:
-            self.bias = None
+        _set_buffers(self, torch.cat([p.bias for p in parts], dim=0).contiguous() if parts[0].bias is not None else None,
+                     wq=torch.cat([p.wq for p in parts], dim=0).contiguous(), ws=torch.cat([p.ws for p in parts], dim=0).contiguous())
 
     @classmethod
     def from_linears(cls, *linears: nn.Linear) -> "FusedQLinear":
@@ -601,22 +585,37 @@ def is_plain_linear(mod: nn.Module) -> bool:
     return isinstance(mod, nn.Linear) and type(mod).forward is nn.Linear.forward
 
 
+def _swap_children(model: nn.Module, visit) -> int:
+    """The tree walk of the swap_* functions.  visit(name, child), for every child in turn, answers a module to put in the child's place (counted once), a count — the
+    child is settled: converted in place (1) or to be left alone (0) — or None: not a candidate, its own children are walked.  Returns the sum of the counts."""
+    n = 0
+    for name, child in list(model.named_children()):
+        r = visit(name, child)
+        if r is None:
+            n += _swap_children(child, visit)
+        elif isinstance(r, nn.Module):
+            setattr(model, name, r)
+            n += 1
+        else:
+            n += r
+    return n
+
+
 def swap_linears(model: nn.Module, predicate=None, fuse_gated_mlp: bool = False) -> nn.Module:
     """Replace every nn.Linear (for which predicate(name, module) is true) by qlinear, in place; Hugging Face Conv1D layers (GPT-2: weight stored [K, N]) likewise,
     through qlinear.from_kn_weight (per-channel quantisation along the strided axis, kernel K2).  A subclass of nn.Linear with a forward of its own is not a linear
     layer to this function (is_plain_linear).
     fuse_gated_mlp=True additionally replaces whole gated-MLP blocks (gate_proj / up_proj / down_proj + SiLU, the
     Llama-family MLP) by GatedMLP: one fused gate+up GEMM, silu*mul fused into the quantisation, the down GEMM."""
-    for name, child in list(model.named_children()):
+    def visit(name, child):
         if fuse_gated_mlp and (predicate is None or predicate(name, child)):
             fused = _as_gated_mlp(child)
             if fused is not None:
-                setattr(model, name, fused)
-                continue
+                return fused
         if is_plain_linear(child) and (predicate is None or predicate(name, child)):
-            setattr(model, name, qlinear.from_linear(child))
-        elif _is_conv1d(child) and (predicate is None or predicate(name, child)):
-            setattr(model, name, qlinear.from_kn_weight(child.weight, child.bias))      # Hugging Face GPT-2's Conv1D: y = x @ W[K, N] + b
-        else:
-            swap_linears(child, predicate, fuse_gated_mlp)
+            return qlinear.from_linear(child)
+        if _is_conv1d(child) and (predicate is None or predicate(name, child)):
+            return qlinear.from_kn_weight(child.weight, child.bias)      # Hugging Face GPT-2's Conv1D: y = x @ W[K, N] + b
+        return None
+    _swap_children(model, visit)
     return model

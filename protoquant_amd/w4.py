@@ -23,13 +23,19 @@ convert_checkpoint for packed weights, dense or expert (the modules' state_dict 
 64 grouped rows expand and run the int8 tiles), RotatedQLinear with W4 weights, zero points, other group sizes, calibration, float-activation weight-only GEMMs."""
 from __future__ import annotations
 
+import importlib
+
 import torch
 from torch import nn
 
 from . import _lib as L
 from .moe import GroupedQLinear, MoEGatedMLP
-from .qlinear import _check_operand, _round_k, _workspace, is_plain_linear, qlinear, qlinear_s8, qlinear_s8_grouped
+from .qlinear import (_check_operand, _epilogue_operands, _grouped_rows, _module_of, _out, _quantize_zero_tailed, _round_k, _set_buffers, _swap_children,
+                      _zero_tailed, is_plain_linear, qlinear, qlinear_s8, qlinear_s8_grouped)
 from .qtensor import QTensor, _launch, _on_gpu, _ptr
+
+# qlinear.py itself (the package attribute `qlinear` is the class): its _workspace is looked up at every call, so whatever replaces qlinear._workspace serves the expand paths
+_QL = importlib.import_module(".qlinear", __package__)
 
 GROUP = 128
 STREAM_ROWS_MAX = 64      # rows the weight-streaming int4 kernel serves (pq_qlinear_w4 refuses more)
@@ -45,9 +51,11 @@ def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
 
 def _packed(what: str, w4: torch.Tensor, gs: torch.Tensor):
     """the checks of a packed weight: (w4 as the kernels walk it, N, Kp)"""
-    _on_gpu(what, w4=w4, gs=gs)
+    if not (w4.is_cuda and gs.is_cuda):
+        _on_gpu(what, w4=w4, gs=gs)
     dev = w4.device
-    _check_operand(w4, "w4", dev, torch.uint8); _check_operand(gs, "gs", dev, torch.uint8)
+    if w4.dtype != torch.uint8 or gs.dtype != torch.uint8 or gs.device != dev:
+        _check_operand(w4, "w4", dev, torch.uint8); _check_operand(gs, "gs", dev, torch.uint8)
     if w4.dim() != 2 or w4.shape[1] == 0 or w4.shape[1] % (GROUP // 2):
         raise ValueError(f"{what}: w4 must be uint8 [N, Kp / 2] with Kp a positive multiple of {GROUP}, got shape {tuple(w4.shape)}")
     N, G = w4.shape[0], w4.shape[1] // (GROUP // 2)
@@ -92,7 +100,8 @@ def w4_expand(w4: torch.Tensor, gs: torch.Tensor, K: int | None = None) -> torch
 
 
 def _codes(what: str, xq: torch.Tensor, kp: int) -> torch.Tensor:
-    _on_gpu(what, xq=xq)
+    if not xq.is_cuda:
+        _on_gpu(what, xq=xq)
     xq = _aligned_rows(xq)
     _check_operand(xq, "xq", xq.device, torch.int8)
     if xq.shape[1] != kp:
@@ -124,20 +133,14 @@ def qlinear_w4(xq: torch.Tensor, xs: torch.Tensor, w4: torch.Tensor, gs: torch.T
     xq = _codes(what, xq, kp)
     M, dev = xq.shape[0], xq.device
     code = L.dtype_code(out_dtype)
-    if bias is not None and bias.dtype != out_dtype:
-        bias = bias.to(out_dtype)
-    _check_operand(xs, "xs", dev, torch.float32, M); _check_operand(ws, "ws", dev, torch.float32, N)
-    if bias is not None:
-        _check_operand(bias, "bias", dev, out_dtype, N)
+    bias = _epilogue_operands(dev, out_dtype, xs, M, ws, bias, per=N)
     if out is not None:
-        _check_operand(out, "out", dev, out_dtype)
-        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
+        _out(out, M, N, dev, out_dtype)
     if M > min(stream_rows, STREAM_ROWS_MAX) and N:
         # the workspace is ONE buffer per (device, stream), and qlinear_s8 takes its split-K slabs from the front of it: W8 goes behind them
         with torch.cuda.device(dev):
             front = (L.lib().pq_qlinear_workspace_bytes(M, N, kp) + 255) & ~255
-        w8 = _workspace(dev, front + N * kp)[front:front + N * kp].view(torch.int8).view(N, kp)
+        w8 = _QL._workspace(dev, front + N * kp)[front:front + N * kp].view(torch.int8).view(N, kp)
         _expand_into(what, w4, gs, N, kp, w8)
         return qlinear_s8(xq, xs, w8, ws, bias, out_dtype, out)
     y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
@@ -158,30 +161,19 @@ class QLinearW4(qlinear):
         nn.Module.__init__(self)
         self.in_features, self.out_features, self.stream_rows = in_features, out_features, STREAM_ROWS_MAX
         kp = _round_k(in_features)
-        self.register_buffer("w4", torch.zeros((out_features, kp // 2), dtype=torch.uint8, device=device))
-        self.register_buffer("gs", torch.ones(((out_features + 3) // 4, kp // GROUP, 4), dtype=torch.uint8, device=device))
-        self.register_buffer("ws", torch.ones((out_features,), dtype=torch.float32, device=device))
-        if bias:
-            self.register_buffer("bias", torch.zeros((out_features,), dtype=dtype or torch.bfloat16, device=device))
-        else:
-            self.bias = None
+        _set_buffers(self, torch.zeros((out_features,), dtype=dtype or torch.bfloat16, device=device) if bias else None,
+                     w4=torch.zeros((out_features, kp // 2), dtype=torch.uint8, device=device),
+                     gs=torch.ones(((out_features + 3) // 4, kp // GROUP, 4), dtype=torch.uint8, device=device),
+                     ws=torch.ones((out_features,), dtype=torch.float32, device=device))
 
     @classmethod
     def from_qlinear(cls, m: qlinear) -> "QLinearW4":
         """the level-2 codes of m's int8 weight (w4_pack); ws and bias are m's own tensors"""
         if isinstance(m, QLinearW4) or not isinstance(m, qlinear) or not getattr(m, "code_fed", True):
             raise TypeError(f"QLinearW4.from_qlinear: expected a plain qlinear, got {type(m).__name__}")
-        r = cls.__new__(cls)
-        nn.Module.__init__(r)
-        r.in_features, r.out_features, r.stream_rows = m.in_features, m.out_features, STREAM_ROWS_MAX
         w4, gs = w4_pack(m.wq)
-        r.register_buffer("w4", w4)
-        r.register_buffer("gs", gs)
-        r.register_buffer("ws", m.ws)
-        if m.bias is not None:
-            r.register_buffer("bias", m.bias)
-        else:
-            r.bias = None
+        r = _module_of(cls, m.bias, w4=w4, gs=gs, ws=m.ws)
+        r.in_features, r.out_features, r.stream_rows = m.in_features, m.out_features, STREAM_ROWS_MAX
         return r
 
     @classmethod
@@ -190,31 +182,20 @@ class QLinearW4(qlinear):
         return cls.from_qlinear(qlinear.from_linear(lin))
 
     def forward(self, x) -> torch.Tensor:
-        K, N = self.in_features, self.out_features
+        K = self.in_features
         if x.shape[-1] != K:
             raise ValueError(f"QLinearW4: expected last dim {K}, got {x.shape[-1]}")
-        kp = _round_k(K)
+        if isinstance(x, QTensor) and x.axis != 1:
+            raise ValueError("QLinearW4: a QTensor input must be quantised per token (axis=-1)")
+        kp = _round_k(K)          # (zero-padded K: the packed tail holds zeros, so do the codes)
         if isinstance(x, QTensor):
-            if x.axis != 1:
-                raise ValueError("QLinearW4: a QTensor input must be quantised per token (axis=-1)")
             buf, xs, out_dtype = x.int_data.reshape(-1, K), x.scale, x.orig_dtype
-            if kp != K:                                   # zero-padded K: the packed tail holds zeros, so do the codes
-                src, buf = buf, torch.empty((buf.shape[0], kp), dtype=torch.int8, device=buf.device)
-                buf[:, :K].copy_(src)
-                buf[:, K:].zero_()
-        else:
-            L.require_gpu(x, "QLinearW4(x)")
-            code = L.dtype_code(x.dtype)
-            x2 = L.row_major_2d(x.reshape(-1, K))
-            M = x2.shape[0]
-            buf = torch.empty((M, kp), dtype=torch.int8, device=x.device)
             if kp != K:
-                buf[:, K:].zero_()
-            xs = torch.empty((M,), dtype=torch.float32, device=x.device)
-            _launch("quantize", x.device, L.lib().pq_quant_rowwise, x2.data_ptr(), code, M, K, L.ld(x2), buf.data_ptr(), kp, xs.data_ptr(), L.stream_ptr(x))
-            out_dtype = x.dtype
+                buf = _zero_tailed(buf, kp)
+        else:
+            (buf, xs), out_dtype = _quantize_zero_tailed(x, kp, "QLinearW4(x)"), x.dtype
         y = qlinear_w4(buf, xs, self.w4, self.gs, self.ws, self.bias, out_dtype, stream_rows=self.stream_rows)
-        return y.reshape(*x.shape[:-1], N)
+        return y.reshape(*x.shape[:-1], self.out_features)
 
     def extra_repr(self):
         return f"{super().extra_repr()}, w4, stream_rows={self.stream_rows}"
@@ -224,24 +205,23 @@ def swap_linears_w4(model: nn.Module, predicate=None) -> int:
     """Replace every nn.Linear of `model` (in place) that is_plain_linear admits and for which predicate(name, module) is true (None: all) by a QLinearW4; returns the
     number replaced (a second call: 0).  `name` is the child's name in its parent, as in swap_linears.  A module that already is a qlinear is never touched.  Opt-in; call
     it BEFORE swap_linears (which then takes the remaining nn.Linear layers) and the fuse_* entries."""
-    n = 0
-    for name, child in list(model.named_children()):
+    def visit(name, child):
         if isinstance(child, qlinear):
-            continue
+            return 0
         if is_plain_linear(child) and (predicate is None or predicate(name, child)):
-            setattr(model, name, QLinearW4.from_linear(child))
-            n += 1
-        else:
-            n += swap_linears_w4(child, predicate)
-    return n
+            return QLinearW4.from_linear(child)
+        return None
+    return _swap_children(model, visit)
 
 
 # ---- the experts of a mixture-of-experts layer: E packed weights stacked, the grouped contract of qlinear_s8_grouped_stream (C-ABI pq_qlinear_w4_grouped_stream)
 def _grouped_call(what: str, xq, w4, gs, offsets, row_index):
     """the checks of the grouped W4 entries: (xq, w4 as the kernel walks it, E, N, Kp, M_total, the C-ABI's operand arguments up to gs_expert_stride)"""
-    _on_gpu(what, xq=xq, w4=w4, gs=gs)
+    if not (xq.is_cuda and w4.is_cuda and gs.is_cuda):
+        _on_gpu(what, xq=xq, w4=w4, gs=gs)
     dev = xq.device
-    _check_operand(w4, "w4", dev, torch.uint8); _check_operand(gs, "gs", dev, torch.uint8)
+    if w4.dtype != torch.uint8 or gs.dtype != torch.uint8 or w4.device != dev or gs.device != dev:
+        _check_operand(w4, "w4", dev, torch.uint8); _check_operand(gs, "gs", dev, torch.uint8)
     if w4.dim() != 3 or w4.shape[0] == 0 or w4.shape[2] == 0 or w4.shape[2] % (GROUP // 2):
         raise ValueError(f"{what}: w4 must be uint8 [E, N, Kp / 2] with Kp a positive multiple of {GROUP}, got shape {tuple(w4.shape)}")
     E, N, G = w4.shape[0], w4.shape[1], w4.shape[2] // (GROUP // 2)
@@ -251,16 +231,8 @@ def _grouped_call(what: str, xq, w4, gs, offsets, row_index):
     if w4.stride(2) != 1 or w4.data_ptr() % 16 or (N > 1 and w4.stride(1) % 16) or (E > 1 and w4.stride(0) % 16):
         w4 = w4.contiguous()
     xq = _codes(what, xq, G * GROUP)
-    _check_operand(offsets, "offsets", dev, torch.int32, E + 1)
-    M = xq.shape[0]
-    if row_index is not None:
-        if row_index.dim() != 1:
-            raise ValueError(f"row_index must be a vector, got shape {tuple(row_index.shape)}")
-        _check_operand(row_index, "row_index", dev, torch.int32, row_index.numel())
-        M = row_index.numel()
-    ldw4 = w4.stride(1) if N > 1 else G * (GROUP // 2)
-    args = (xq.data_ptr(), L.ld(xq), _ptr(row_index), xq.shape[0]), (w4.data_ptr(), ldw4, w4.stride(0) if E > 1 else max(N, 1) * ldw4, gs.data_ptr(), quads * G * 4)
-    return xq, w4, E, N, G * GROUP, M, args
+    x_args, w_args = _grouped_rows(xq, w4, G * (GROUP // 2), offsets, row_index)
+    return xq, w4, E, N, G * GROUP, xq.shape[0] if row_index is None else row_index.numel(), (x_args, (*w_args, gs.data_ptr(), quads * G * 4))
 
 
 def int_mm_w4_grouped(xq: torch.Tensor, w4: torch.Tensor, gs: torch.Tensor, offsets: torch.Tensor, row_index: torch.Tensor | None = None) -> torch.Tensor:
@@ -290,22 +262,10 @@ def qlinear_w4_grouped(xq: torch.Tensor, xs: torch.Tensor, w4: torch.Tensor, gs:
     xq, w4, E, N, kp, M, (x_args, w_args) = _grouped_call(what, xq, w4, gs, offsets, row_index)
     dev = xq.device
     code = L.dtype_code(out_dtype)
-    _check_operand(xs, "xs", dev, torch.float32, M)
-    _check_operand(ws, "ws", dev, torch.float32)
-    if bias is not None:
-        if bias.dtype != out_dtype:
-            bias = bias.to(out_dtype)
-        _check_operand(bias, "bias", dev, out_dtype)
-    for t, name in ((ws, "ws"), (bias, "bias")):
-        if t is not None and (tuple(t.shape) != (E, N) or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous [{E}, {N}] tensor, got shape {tuple(t.shape)} stride {t.stride()}")
-    if out is not None:
-        _check_operand(out, "out", dev, out_dtype)
-        if out.dim() != 2 or out.shape != (M, N) or (N > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a row-major [{M}, {N}] tensor, got {tuple(out.shape)} stride {out.stride()}")
-    y = out if out is not None else torch.empty((M, N), dtype=out_dtype, device=dev)
+    bias = _epilogue_operands(dev, out_dtype, xs, M, ws, bias, per=(E, N))
+    y = torch.empty((M, N), dtype=out_dtype, device=dev) if out is None else _out(out, M, N, dev, out_dtype)
     if M > min(stream_rows, STREAM_ROWS_MAX) and N:
-        w8 = _workspace(dev, E * N * kp)[:E * N * kp].view(torch.int8).view(E, N, kp)
+        w8 = _QL._workspace(dev, E * N * kp)[:E * N * kp].view(torch.int8).view(E, N, kp)
         if N % 4 == 0 and (E == 1 or w4.stride(0) == N * w4.stride(1)):
             _expand_into(what, w4.as_strided((E * N, kp // 2), (w4.stride(1), 1)), gs, E * N, kp, w8)
         else:
@@ -313,7 +273,7 @@ def qlinear_w4_grouped(xq: torch.Tensor, xs: torch.Tensor, w4: torch.Tensor, gs:
                 _expand_into(what, w4[e], gs[e], N, kp, w8[e])
         return qlinear_s8_grouped(xq, xs, w8, ws, bias, offsets, out_dtype, row_index=row_index, out=y)
     if M and N:
-        _launch(what, dev, L.lib().pq_qlinear_w4_grouped_stream, *x_args[:4], xs.data_ptr(), *w_args, ws.data_ptr(), _ptr(bias), offsets.data_ptr(), E, M, N, kp,
+        _launch(what, dev, L.lib().pq_qlinear_w4_grouped_stream, *x_args, xs.data_ptr(), *w_args, ws.data_ptr(), _ptr(bias), offsets.data_ptr(), E, M, N, kp,
                 y.data_ptr(), L.ld(y), code, L.stream_ptr(xq))
     return y
 
@@ -330,13 +290,10 @@ class GroupedQLinearW4(nn.Module):
         super().__init__()
         self.num_experts, self.in_features, self.out_features = num_experts, in_features, out_features
         kp = _round_k(in_features)
-        self.register_buffer("w4", torch.zeros((num_experts, out_features, kp // 2), dtype=torch.uint8, device=device))
-        self.register_buffer("gs", torch.ones((num_experts, (out_features + 3) // 4, kp // GROUP, 4), dtype=torch.uint8, device=device))
-        self.register_buffer("ws", torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
-        if bias:
-            self.register_buffer("bias", torch.zeros((num_experts, out_features), dtype=dtype or torch.bfloat16, device=device))
-        else:
-            self.bias = None
+        _set_buffers(self, torch.zeros((num_experts, out_features), dtype=dtype or torch.bfloat16, device=device) if bias else None,
+                     w4=torch.zeros((num_experts, out_features, kp // 2), dtype=torch.uint8, device=device),
+                     gs=torch.ones((num_experts, (out_features + 3) // 4, kp // GROUP, 4), dtype=torch.uint8, device=device),
+                     ws=torch.ones((num_experts, out_features), dtype=torch.float32, device=device))
 
     @classmethod
     def from_grouped(cls, m: GroupedQLinear) -> "GroupedQLinearW4":
@@ -345,20 +302,12 @@ class GroupedQLinearW4(nn.Module):
         if not isinstance(m, GroupedQLinear):
             raise TypeError(f"GroupedQLinearW4.from_grouped: expected a GroupedQLinear, got {type(m).__name__}")
         E, N, K = m.num_experts, m.out_features, m.in_features
-        r = cls.__new__(cls)
-        nn.Module.__init__(r)
-        r.num_experts, r.in_features, r.out_features = E, K, N
         w4, gs = w4_pack(m.wq.reshape(E * N, K))
         G, quads = gs.shape[1], (N + 3) // 4
         g = gs.permute(0, 2, 1).reshape(-1, G)[:E * N].reshape(E, N, G)          # g[e, n, j]
         g = torch.cat([g, g.new_ones((E, quads * 4 - N, G))], dim=1)
-        r.register_buffer("w4", w4.view(E, N, -1))
-        r.register_buffer("gs", g.view(E, quads, 4, G).permute(0, 1, 3, 2).contiguous())
-        r.register_buffer("ws", m.ws)
-        if m.bias is not None:
-            r.register_buffer("bias", m.bias)
-        else:
-            r.bias = None
+        r = _module_of(cls, m.bias, w4=w4.view(E, N, -1), gs=g.view(E, quads, 4, G).permute(0, 1, 3, 2).contiguous(), ws=m.ws)
+        r.num_experts, r.in_features, r.out_features = E, K, N
         return r
 
     @classmethod
@@ -390,12 +339,11 @@ def swap_moe_experts_w4(model: nn.Module, predicate=None) -> int:
     GroupedQLinearW4.from_grouped; returns the number of MoEGatedMLP modules converted (a second call: 0).  `name` is the module's name in its parent, as in
     swap_linears_w4.  Opt-in; call it AFTER swap_moe_experts (which makes the MoEGatedMLP modules).  Gate kinds, the router, fuse_moe_routers and torch_plumbing are
     untouched: MoEGatedMLP reads only num_experts / in_features / out_features of its members and calls them."""
-    n = 0
-    for name, child in list(model.named_children()):
-        if isinstance(child, MoEGatedMLP):
-            if isinstance(child.gate_up, GroupedQLinear) and isinstance(child.down, GroupedQLinear) and (predicate is None or predicate(name, child)):
-                child.gate_up, child.down = GroupedQLinearW4.from_grouped(child.gate_up), GroupedQLinearW4.from_grouped(child.down)
-                n += 1
-        else:
-            n += swap_moe_experts_w4(child, predicate)
-    return n
+    def visit(name, child):
+        if not isinstance(child, MoEGatedMLP):
+            return None
+        if not (isinstance(child.gate_up, GroupedQLinear) and isinstance(child.down, GroupedQLinear) and (predicate is None or predicate(name, child))):
+            return 0
+        child.gate_up, child.down = GroupedQLinearW4.from_grouped(child.gate_up), GroupedQLinearW4.from_grouped(child.down)
+        return 1
+    return _swap_children(model, visit)

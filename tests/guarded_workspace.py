@@ -98,7 +98,8 @@ class Guarded:
 
 def patched_allocators(monkeypatch, fill=GARBAGE):
     """Replace protoquant_amd.qlinear._workspace, the name moe.py bound to it at import, RcclColumnGather._workspace and RcclRowReduceScatter._workspace by allocators
-    that return the interior of a fresh Guarded of exactly the requested size.  Returns the list every Guarded handed out is appended to (it also keeps them alive until
+    that return the interior of a fresh Guarded of exactly the requested size.  w4.py binds no allocator of its own: its expand paths call qlinear._workspace through the
+    qlinear module at every call, so the first patch reaches them.  Returns the list every Guarded handed out is appended to (it also keeps them alive until
     the side stream of an overlapped exchange is through with them)."""
     import importlib
     qlinear = importlib.import_module("protoquant_amd.qlinear")      # (the package attribute of that name is the qlinear CLASS)

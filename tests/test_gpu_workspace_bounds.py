@@ -16,7 +16,7 @@ FSK t + FSK): 2 / 4 words per tile; the slabs start at fsk_counter_bytes of the 
 one the launcher zeroed, whatever the workspace held.
 
 Each test synchronises twice: once behind step 1 of all its shapes (step 3 must not start on a row that failed step 1), once at its end; every check in between is a flag
-left on the device.  Measured wall time of the file on one MI355X: 7.7 s for its 29 tests — tests/test_gpu_gemm_edges.py takes minutes.
+left on the device.  Measured wall time of the file on one MI355X: 6.5 s for its 32 tests — tests/test_gpu_gemm_edges.py takes minutes.
 
 A shape the planner never splits: M N < 128^2 (300 x 1) goes to the generic kernel, which has no split form, whatever slice count is forced.  The query is 0 wherever
 qlinear_core would not look at a workspace, and a call that is handed one anyway leaves it alone (NEVER_TILED); the N = 1 tail of the reduction pass is covered by (16384, 1).
@@ -38,7 +38,7 @@ from tests.guarded_workspace import Guarded, patched_allocators
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = "29 tests in 7.7 s (pytest's own figure, one MI355X, the file run alone; the slowest, 3.7 s, is the first exchange row: it creates the RCCL communicator)"
+MEASURED = "32 tests in 6.5 s (pytest's own figure, one MI355X, the file run alone; the slowest, 3.7 s, is the first exchange row: it creates the RCCL communicator)"
 PQ_OK, PQ_ERR_WORKSPACE = 0, 5
 SLAB = 256 * 256 * 4
 TILED = (b"sp256_16x16x64", b"sp128x256_16x16x64", b"ring128_16x16x64")      # qlinear_core's `tiled`: the dispatches that may split K
@@ -653,6 +653,47 @@ def test_flow_kslabs_with_forced_fused_split_k(monkeypatch, pq_opt):
     pq_opt("PQ_FSK", "2")
     handed = _stock_then_guarded(monkeypatch, lambda: pq.qlinear_s8_kslabs(stacked, xs, wq, ws, None, torch.bfloat16), "qlinear_s8_kslabs")
     assert [h.nbytes for h in handed] == [fsk_bytes(M, N, 2)]
+
+
+def _w4_operands(E, N, Kp, M, seed):
+    """random codes and scales; the packed experts (per expert what w4_pack gives) and the int8 weights they stand for"""
+    import protoquant_amd as pq
+    g = torch.Generator().manual_seed(seed)
+    wq = torch.randint(-127, 128, (E, N, Kp), generator=g, dtype=torch.int8).cuda()
+    xq = torch.randint(-128, 128, (M, Kp), generator=g, dtype=torch.int8).cuda()
+    xs, ws = (torch.rand(M, generator=g) * 0.01 + 1e-4).cuda(), (torch.rand(E, N, generator=g) * 0.01 + 1e-4).cuda()
+    bias = torch.randn(E, N, generator=g).to(torch.bfloat16).cuda()
+    packs = [pq.w4_pack(wq[e]) for e in range(E)]
+    w4, gs = torch.stack([p[0] for p in packs]), torch.stack([p[1] for p in packs])
+    return xq, xs, w4, gs, torch.stack([pq.w4_expand(*p) for p in packs]), ws, bias
+
+
+def test_flow_qlinear_w4_expand(monkeypatch, pq_opt):
+    """The dense expand path carves W8 out of the shared workspace BEHIND qlinear_s8's own bytes: front = align256(the query).  65 x 20 x 256 plans no split, forced or not
+    (M N < 128^2 goes to the generic kernel: NEVER_TILED), so the run with a non-empty front is dyn-twopass's 65 x 255 over 15 K-tiles under PQ_FORCE_SPLITK=3."""
+    import protoquant_amd as pq
+    for M, N, Kp, rows, S in ((65, 20, 256, {}, 0), (3, 20, 256, {"stream_rows": 0}, 0), (65, 255, kt(15), {}, 3)):
+        if S:
+            pq_opt("PQ_FORCE_SPLITK", str(S))
+        query = _hip().pq_qlinear_workspace_bytes(M, N, Kp)
+        assert query == S * M * N * 4, f"{M} x {N} x {Kp} with {S} forced slices: the query reports {query} bytes"
+        xq, xs, w4, gs, w8, ws, bias = _w4_operands(1, N, Kp, M, 11 + M + N)
+        run = lambda: pq.qlinear_w4(xq, xs, w4[0], gs[0], ws[0], bias[0], torch.bfloat16, **rows)          # noqa: E731
+        handed = _stock_then_guarded(monkeypatch, run, f"qlinear_w4 above stream_rows, {M} x {N} x {Kp}, {S} slices")
+        assert [g.nbytes for g in handed] == [align256(query) + N * Kp] + ([query] if query else [])
+        assert torch.equal(run(), pq.qlinear_s8(xq, xs, w8[0], ws[0], bias[0], torch.bfloat16))
+
+
+@pytest.mark.parametrize("N", (20, 6), ids=("one expand launch", "an expand per expert"))
+def test_flow_qlinear_w4_grouped_expand(N, monkeypatch):
+    import protoquant_amd as pq
+    E_, Kp, M = 3, 256, 65
+    xq, xs, w4, gs, w8, ws, bias = _w4_operands(E_, N, Kp, M, 17 + N)
+    offsets = torch.tensor([0, 40, 40, 65], dtype=torch.int32, device="cuda")          # (expert 1 owns no row)
+    run = lambda: pq.qlinear_w4_grouped(xq, xs, w4, gs, ws, bias, offsets, torch.bfloat16)          # noqa: E731
+    handed = _stock_then_guarded(monkeypatch, run, f"qlinear_w4_grouped above stream_rows, N = {N}")
+    assert [g.nbytes for g in handed] == [E_ * N * Kp]
+    assert torch.equal(run(), pq.qlinear_s8_grouped(xq, xs, w8, ws, bias, offsets, torch.bfloat16))
 
 
 def test_flow_moe_forward_with_the_three_launch_route(monkeypatch):
